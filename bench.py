@@ -11,12 +11,16 @@ Workload = BASELINE.json's metric config: L-DGN, 50-node graphs, 1024 vectorised
 (weak scaling: each rank owns its own 1024 envs, no data-path collective), fp32, dynamic graph (the
 reference CLI default, common.py:51), synthetic connected RGGs + seeded random-init weights.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     - dominant kernel (by HIP-event time inside the step) vs the fp32 MFMA peak
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the headline; --full adds what takes runs of its own:
+  roofline     - dominant kernel (by HIP-event time inside the step) vs the fp32 MFMA peak (+ stage_us, parts, roofline_hbm)
+  sustained    - the same loop for a few seconds of wall time
+  legs         - the other BASELINE configurations, precisions and sizes, timed like the headline
   cpu_baseline - the CPU oracle (torch restatement + Python env restatement) on the host cores, N=1 only
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (see loop_outputs).
 """
 from __future__ import annotations
 
@@ -284,6 +288,57 @@ def timed_run(loop, steps, warmup, device, parallel):
             "decisions": parallel.all_reduce_sum(local_dec, device),
             "episodes": parallel.all_reduce_sum(float(c1["episodes"] - c0["episodes"]), device),
             "errors": parallel.all_reduce_sum(float(c1["errors"]), device)}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _bits(words, n):
+    """[B] or [B, W] int64 node-set bit patterns -> [B, n] 0/1 (node i = bit i % 64 of word i // 64)."""
+    import torch
+    words = words.view(words.shape[0], -1)
+    i = torch.arange(n, device=words.device)
+    return (words[:, i // 64] >> (i % 64)) & 1
+
+
+def loop_outputs(loop) -> dict:
+    """What the timed path handed its caller after its last step (read after the synchronise that ends the timed region):
+    that step's logits and actions, and the env state the next step starts from - observations, active agents, rewards,
+    per-env counters.  Round loop: the logits / actions of the round's (env, agent) rows, ``row_offsets`` [B + 1] delimiting
+    each env's rows (HL-DGN: one logits row per env, actions per (env, node)).  Several streams: one set per sub-batch."""
+    import torch
+    if hasattr(loop, "loops"):
+        return {f"{k}_s{i}": v for i, sub in enumerate(loop.loops) for k, v in loop_outputs(sub).items()}
+    venv = loop.venv
+    if not hasattr(loop, "offsets"):                                  # AEC-order loop: one decision per env
+        out = {"logits": loop.logits, "actions": loop.act, "obs": loop.obs}
+    elif loop.per_env_logits:
+        out = {"logits": loop.logits, "actions": loop.act.view(venv.env_num, venv.n), "obs": venv.obs_matrix(),
+               "active_agents": _bits(loop.live, venv.n)}
+    else:
+        rows = int(loop.offsets[-1])
+        out = {"logits": loop.logits[:rows], "actions": loop.act[:rows], "row_offsets": loop.offsets,
+               "obs": venv.obs_matrix(), "active_agents": _bits(loop.live, venv.n)}
+    out["rewards"] = venv._field(venv.env.rewards, venv.n, torch.float64)
+    out["episode_rewards"] = venv._field(venv.env.episode_rewards, 1, torch.float64)[:, 0]
+    out["counters"] = venv.scalars()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(arrays: dict, path: str, budget: int = DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy: float arrays in their own precision, integers as float64 (exact).  Beyond ``budget`` bytes in all,
+    every array keeps the same seeded sample of its rows on every run (``<name>_rows``: the row indices kept)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in list(arrays.items()):
+        if total > budget and a.ndim and len(a) > 1:
+            # a third of the budget for the rows: their float64 indices take at most twice the rows' bytes
+            keep = max(1, int(len(a) * budget / (3 * total)))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            arrays[name], arrays[f"{name}_rows"] = a[rows], rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def pmc_traffic():
@@ -565,7 +620,14 @@ def main():
                          "per env that wrap (A/B of the stream's cost only; the wrap raises the env's underrun flag)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a 1-GPU box: every rank uses cuda:0 and the gloo backend")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baselines, sustained leg, stage profile / rooflines and the extra legs "
+                         "(each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (several ranks: DIR/rank<r>/)")
     args = ap.parse_args()
+    if not args.full:                         # a plain run does only what the headline needs
+        args.no_cpu_baseline = args.no_extra_legs = args.no_profile = True
     GRAPH_ROUNDS[0] = max(1, args.graph_rounds)
 
     # --gpus N without an external launcher: this process is still GPU-free (no torch.cuda call, no library load), so it
@@ -610,6 +672,8 @@ def main():
     per_rank[rank] = t["local_decisions"] / t["dt_local"]
     per_rank = [parallel.all_reduce_sum(v, device) for v in per_rank]
     supply = loop.supply.describe() if hasattr(loop, "supply") else loop.loops[0].supply.describe()
+    if args.dump_outputs:                     # before anything below runs the loop again
+        write_outputs(loop_outputs(loop), args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))
 
     # ---- sustained leg: the same loop for >= ~2.5 s of wall time (the timed region above is a few ms at the driver's
     # --steps 20, too short for a utilisation sampler to see the GPU busy)

@@ -807,3 +807,41 @@ def test_captured_update_equals_the_eager_update(model, collective):
         twin_net.load_state_dict(net.state_dict())
         assert torch.equal(got, twin_net.hip_forward(torch.cat([obs, idx], 1)))
     assert loop.counters()["errors"] == 0
+
+
+@pytest.mark.parametrize("model,mode", [("l_dgn", "round"), ("hl_dgn", "round"), ("l_dgn", "aec")])
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path, monkeypatch, model, mode):
+    """bench.py --dump-outputs: what the last timed step handed its caller.  The round loop's logits / actions hold one row per
+    agent that was active in that round (per env: row_offsets; HL-DGN: one logits row per env), and two workloads built from
+    the same arguments write identical float32 / float64 files."""
+    import bench
+    from melissa_amd import parallel
+    # a few settling rounds instead of 512 (the outputs of a timed step are checked, not a settled loop's rate); 50 nodes: the
+    # benchmark's pool of 1024 connected random geometric graphs takes minutes to draw at 20 nodes, under a second at 50
+    monkeypatch.setattr(bench, "SETTLE_ROUNDS", 8)
+    dev, B, n = torch.device("cuda", 0), 64, 50
+    for k in range(2):
+        net, venv, loop = bench.build_workload(dev, 0, B, n, model, mode, True, 1)
+        bench.timed_run(loop, 4, 2, dev, parallel)
+        before = bench.loop_outputs(loop)
+        t = bench.timed_run(loop, 1, 0, dev, parallel)
+        out = bench.loop_outputs(loop)
+        assert t["errors"] == 0 and np.isfinite(out["logits"]).all()
+        if mode == "aec":
+            assert out["logits"].shape == (B, 2) and out["obs"].shape == (B, 8 * n + 1) and set(np.unique(out["actions"])) <= {0, 1}
+        elif model == "hl_dgn":
+            acted = before["active_agents"].astype(bool)
+            assert out["logits"].shape == (B, 2) and set(np.unique(out["actions"][acted])) <= {0, 1}
+        else:
+            per_env = before["active_agents"].sum(axis=1)
+            np.testing.assert_array_equal(np.diff(out["row_offsets"]), per_env)
+            assert out["logits"].shape == (per_env.sum(), 2) and set(np.unique(out["actions"])) <= {0, 1}
+        bench.write_outputs(out, str(tmp_path / f"run{k}"))
+        del net, venv, loop
+        torch.cuda.empty_cache()
+    names = sorted(p.name for p in (tmp_path / "run0").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "run1").iterdir()) and "logits.npy" in names
+    for name in names:
+        a, b = np.load(tmp_path / "run0" / name), np.load(tmp_path / "run1" / name)
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, b, err_msg=name)

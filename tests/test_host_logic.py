@@ -1,5 +1,7 @@
 """Host-side logic that needs no GPU: episode sampling mirrors World.reset's RNG protocol, pool packing,
 graph helpers, network drop-in surface (ctor / state_dict keys / errors / torch path), policy helpers."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -12,6 +14,7 @@ from melissa_amd.policy import DQNPolicy, MultiAgentSharedPolicy
 from oracle import env_oracle as eo
 from oracle import net_oracle as no
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DUEL = lambda: ({"hidden_sizes": [128, 128]}, {"hidden_sizes": [128, 128]})
 
 
@@ -70,7 +73,7 @@ def test_network_dropin_surface():
         HLDGNNetwork(5, 128, 2, 4, 20, aggregator="median", dueling_param=DUEL())
     dr = DGNRNetwork(5, 128, 2, 4, 20, dueling_param=DUEL(), backend="torch")
     assert set(dr.state_dict()) == set(no.init_weights("dgn_r")) and sum(p.numel() for p in dr.parameters()) == 1660675
-    g = np.load("tests/golden/net_golden_n20.npz")
+    g = np.load(os.path.join(GOLDEN, "net_golden_n20.npz"))
     dr.load_state_dict(no.init_weights("dgn_r", seed=int(g["weight_seed"]) + 2))
     with torch.enable_grad():
         out, _ = dr(g["obs"])
@@ -86,7 +89,7 @@ def test_network_dropin_surface():
 
 
 def test_torch_path_matches_oracle_and_has_gradients():
-    g = np.load("tests/golden/net_golden_n12.npz")
+    g = np.load(os.path.join(GOLDEN, "net_golden_n12.npz"))
     sd = no.init_weights("l_dgn", seed=int(g["weight_seed"]), random_conv_bias=True)
     net = LDGNNetwork(5, 128, 2, 4, 12, dueling_param=DUEL(), backend="auto")     # grad enabled -> torch path on CPU
     net.load_state_dict(sd)
@@ -324,6 +327,32 @@ def test_bench_cpu_baseline_variants_run():
     assert fl["conv2_lin"] == 2.0 * 15 * 512 * 512 and fl["conv1_lin"] == 2.0 * 30 * 512 * 128
     ft = bench.stage_flops((10.0, 20.0, 5.0), table_rows=2000)                  # node-feature table: priced at its rows
     assert ft["conv1_lin"] == 2.0 * 4000 * 512 * 128 and ft["encoder"] == 2000 * 34048 and ft["conv2_lin"] == fl["conv2_lin"]
+
+
+def test_bench_write_outputs_dtypes_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 stays float32, everything else is float64 (integers exact); past the byte budget every
+    array keeps the same seeded sample of its rows, with the indices kept beside it.  Node sets unpack to 0/1 per node."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"logits": rng.standard_normal((5000, 2)).astype(np.float32), "actions": rng.integers(0, 2, 5000).astype(np.int32),
+              "rewards": rng.standard_normal((5000, 20)), "counters": rng.integers(-5, 1 << 20, (5000, 16)).astype(np.int32)}
+    bench.write_outputs(arrays, str(tmp_path / "all"))
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == (np.float32 if a.dtype == np.float32 else np.float64)
+        np.testing.assert_array_equal(got, a)
+    budget = 200_000
+    for run in ("s0", "s1"):
+        bench.write_outputs(arrays, str(tmp_path / run), budget=budget)
+    files = sorted((tmp_path / "s0").iterdir())
+    assert sum(f.stat().st_size for f in files) <= budget + 128 * len(files)        # (+ the .npy headers)
+    for f in files:
+        np.testing.assert_array_equal(np.load(f), np.load(tmp_path / "s1" / f.name))
+    rows = np.load(tmp_path / "s0" / "rewards_rows.npy").astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "s0" / "rewards.npy"), arrays["rewards"][rows])
+    words = torch.tensor([[0b101, 0], [-(1 << 63), 1]], dtype=torch.int64)             # bit 63 of word 0 is the sign bit
+    bits = bench._bits(words, 65).numpy()
+    assert bits[0].nonzero()[0].tolist() == [0, 2] and bits[1].nonzero()[0].tolist() == [63, 64]
 
 
 def test_graph_size_limits_and_two_word_node_sets():

@@ -103,7 +103,7 @@ def test_visible_gpus_counts_only_devices_this_process_can_open(tmp_path):
 
 
 PARENT_GUARD = """
-import builtins, os
+import builtins, os, sys
 _real = builtins.__import__
 def guarded(name, *a, **k):
     if name.split(".")[0] == "torch":
@@ -115,6 +115,9 @@ if "RANK" not in os.environ:            # the PARENT: torch (any HIP entry point
     builtins.__import__ = guarded
     import ctypes
     ctypes.CDLL = no_library
+else:                                   # a RANK says so at interpreter start: the launcher stops the survivors of a failed rank,
+    sys.stderr.write("rank started\\n")  # so a rank still importing torch when the other fails would leave no line otherwise
+    sys.stderr.flush()
 """
 
 
