@@ -592,6 +592,9 @@ typedef struct mel_round_replay {
     float*    rew;             /* [B, K, N]                                                       */
     int32_t*  episode;         /* [B, K] episode ordinal of the env when the round was played     */
     int32_t*  cursor;          /* [B]    rounds recorded so far (slot = cursor % K)               */
+    uint64_t* active_nb;       /* [B, K, N] optional (NULL = off): info['active_one_hop_neighbors'] of each acting
+                                * agent at ITS next observation (graph.py:198-203, collective_experience_collector.py:270-290),
+                                * written with the world step; 0 for agents that did not act                          */
 } mel_round_replay;
 
 /* Replay sampling in one launch (the learn half's first step, l_dgn.py:246-261 -> [3P] tianshou ReplayBuffer.sample +
@@ -601,7 +604,8 @@ typedef struct mel_round_replay {
  * bootstrap from), act int64, ret float (sum_j discount[j] * rew_j), boot_w float (discount[steps], 0 when the agent
  * terminated inside the window), env / slot / agent int64.  discount: HOST float [n_step + 1] = gamma^j (copied into the launch).
  * Draws are a counter-based function of (seed, *draw_counter, sample index); the launch increments *draw_counter (device
- * uint64), so replaying it from a HIP graph keeps drawing new batches.  scratch: device int32 [n_envs * capacity + 1]. */
+ * uint64), so replaying it from a HIP graph keeps drawing new batches.  scratch: device int32 [n_envs * capacity + 1].
+ * out->nb_sibling (optional) needs replay->active_nb, else MEL_ERR_INVALID_ARG. */
 #define MEL_REPLAY_MAX_NSTEP 16
 typedef struct mel_replay_batch {
     float*   obs;
@@ -612,6 +616,8 @@ typedef struct mel_replay_batch {
     int64_t* env;
     int64_t* slot;
     int64_t* agent;
+    uint64_t* nb_sibling;      /* [batch] optional (NULL = off): acted[rec] & (active_nb[rec, agent] | bit(agent)), the
+                                * siblings N-DGN sums over (policies/n_dgn.py:36-47); needs replay->active_nb          */
 } mel_replay_batch;
 mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int32_t n_nodes, int32_t batch, int32_t n_step,
                              const float* discount, uint64_t seed, uint64_t* draw_counter, int32_t* scratch,

@@ -82,12 +82,12 @@ class MelSelect(C.Structure):
 class MelRoundReplay(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("reserved", C.c_int32), ("obs", C.c_void_p), ("obs_next", C.c_void_p),
                 ("acted", C.c_void_p), ("done", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p),
-                ("episode", C.c_void_p), ("cursor", C.c_void_p)]
+                ("episode", C.c_void_p), ("cursor", C.c_void_p), ("active_nb", C.c_void_p)]
 
 
 class MelReplayBatch(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("boot_obs", C.c_void_p), ("act", C.c_void_p), ("ret", C.c_void_p), ("boot_w", C.c_void_p),
-                ("env", C.c_void_p), ("slot", C.c_void_p), ("agent", C.c_void_p)]
+                ("env", C.c_void_p), ("slot", C.c_void_p), ("agent", C.c_void_p), ("nb_sibling", C.c_void_p)]
 
 
 ADAM_MAX_TENSORS = 64

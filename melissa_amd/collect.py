@@ -551,3 +551,23 @@ class MultiAgentCollector(Collector):
         eps = 1.0 if random else (float(getattr(self.policy, "eps", 0.0)) if self.exploration_noise else 0.0)
         self.set_eps(eps)
         return super().collect(n_step=n_step, n_episode=n_episode)
+
+
+class CollectiveExperienceCollector(MultiAgentCollector):
+    """``CollectiveExperienceCollector(agents_num, policy=..., env=..., buffer=None, exploration_noise=False)`` - the collector of
+    the collective scripts (collective_experience_collector.py:20; dgn_r.py, n_dgn_r.py, l_n_dgn_r.py, hl_n_dgn_r.py).  Besides each
+    transition it keeps what the collective losses read: the siblings (``info.indices``, :70-80 - in a round record they are the
+    ``acted`` set) and the ``info`` of the agent's next observation (:270-290), of which N-DGN reads
+    ``active_one_hop_neighbors``.  So the buffer must record neighbours: ``buffer=None`` creates a
+    ``RoundReplay(neighbours=True)`` of ``buffer_rounds`` records per env (1: the reference's default
+    ``VectorReplayBuffer(env_num * agents_num, env_num * agents_num)`` holds one transition per sub-buffer); a given
+    :class:`melissa_amd.replay.RoundReplay` without neighbours raises.  Everything else is :class:`MultiAgentCollector`."""
+
+    def __init__(self, agents_num, buffer=None, buffer_rounds: int = 1, **kwargs):
+        from .replay import RoundReplay
+        env = kwargs.get("env")
+        if buffer is None and env is not None:
+            buffer = RoundReplay(env.env_num, int(agents_num), int(buffer_rounds), env.device, neighbours=True)
+        elif buffer is not None and getattr(buffer, "active_nb", None) is None:
+            raise ValueError("CollectiveExperienceCollector needs a buffer that records neighbours: RoundReplay(..., neighbours=True)")
+        super().__init__(agents_num, buffer=buffer, **kwargs)

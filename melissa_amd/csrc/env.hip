@@ -728,6 +728,20 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
                 MEL_W_FOR(h) if (lane + 64 * h < n)
                     a.replay.rew[rec * n + lane + 64 * h] = ns_mine(live_in, lane, h) ? (float)s.reward[h] : 0.f;
                 if (lane == 0) ns_store<W>(a.replay.done, rec, s.terminated & live_in);
+                if (a.replay.active_nb) {
+                    // info['active_one_hop_neighbors'] of each acting agent at ITS next observation (graph.py:198-203), which
+                    // the collective collector stores with the transition (collective_experience_collector.py:270-290).  Until
+                    // then nothing moves: one_hop and truncated are final, only the dead steps of D = agents & terminated
+                    // remove agents, in id order (graph.py:278-298,359).  A live agent is observed after all of them, a dead
+                    // one at its own dead step, after those of the lower ids of D.
+                    const NodeSet<W> dead = s.agents & s.terminated;
+                    MEL_W_FOR(h) if (lane + 64 * h < n) {
+                        const int i = lane + 64 * h;
+                        const NodeSet<W> gone = ns_test(dead, i) ? (dead & ns_full<W>(i)) : dead;
+                        const NodeSet<W> nb = s.one_hop[h] & ~(s.truncated & ~(s.agents & ~gone));
+                        ns_store<W>(a.replay.active_nb, rec * n + i, ns_mine(live_in, lane, h) ? nb : ns_zero<W>());
+                    }
+                }
             }
             if (r & 1) s.done_count += 1;
             if ((r & 1) && ((r & 2) || s.done_count == n)) {                  // episode over
@@ -1101,6 +1115,13 @@ __global__ __launch_bounds__(1024) void replay_sample_kernel(ReplaySampleArgs a)
         a.out.env[tid] = e, a.out.slot[tid] = k, a.out.agent[tid] = agent;
         a.out.act[tid] = (long long)a.rp.act[((size_t)e * K + k) * a.n + agent];
         a.out.ret[tid] = ret, a.out.boot_w[tid] = bw;
+        if (a.out.nb_sibling) {             // policies/n_dgn.py:36-47: siblings restricted to the one-hop set (+ the agent)
+            const size_t rec = (size_t)e * K + k;
+            for (int w = 0; w < a.W; ++w) {
+                const unsigned long long self = w == (agent >> 6) ? 1ull << (agent & 63) : 0ull;
+                a.out.nb_sibling[(size_t)tid * a.W + w] = a.rp.acted[rec * a.W + w] & (a.rp.active_nb[(rec * a.n + agent) * a.W + w] | self);
+            }
+        }
     }
     __syncthreads();
     const int width = 8 * a.n, row = width + 1;
@@ -1122,6 +1143,8 @@ mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int
         return fail(MEL_ERR_INVALID_ARG, "incomplete replay block");
     if (!out->obs || !out->boot_obs || !out->act || !out->ret || !out->boot_w || !out->env || !out->slot || !out->agent)
         return fail(MEL_ERR_INVALID_ARG, "incomplete replay batch");
+    if (out->nb_sibling && !replay->active_nb)
+        return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: nb_sibling needs a replay that records active_nb");
     if (n_envs < 1 || n_nodes < 1 || n_nodes > MEL_MAX_NODES || batch < 1 || batch > 1024 || n_step < 1 || n_step > MEL_REPLAY_MAX_NSTEP ||
         n_envs * (int64_t)replay->capacity > (1ll << 24))
         return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: batch in [1, 1024], n_step in [1, %d], n_envs * capacity <= 2^24", MEL_REPLAY_MAX_NSTEP);

@@ -38,3 +38,12 @@ class HLDGNNetwork(GraphQNetwork):
         x = (x * dm.reshape(bs * n, 1)).view(bs, n, -1)
         pooled = {"max": lambda t: t.max(dim=1).values, "mean": lambda t: t.mean(dim=1), "add": lambda t: t.sum(dim=1)}
         return self._head(pooled[self.aggregator_name](x))
+
+    def torch_forward_all_agents(self, obs_matrix: torch.Tensor) -> torch.Tensor:
+        """``[g, j] == torch_forward(cat(obs_matrix[g], j))`` for every node j (logits [G, N, A]): the pool runs over the whole
+        graph and nothing reads the controlling agent (hl_dgn.py:97-115), so this is ONE forward per graph, expanded - the dense
+        sibling form of the DGN-R / N-DGN losses (policy.DGNPolicy.loss_backward), gradients through the HIP pool on ROCm."""
+        obs_matrix = obs_matrix.to(self.device)
+        G = obs_matrix.shape[0]
+        q = self.torch_forward(torch.cat([obs_matrix.float(), obs_matrix.new_zeros(G, 1, dtype=torch.float32)], dim=1))
+        return q[:, None, :].expand(G, self.agents_num, q.shape[1])

@@ -219,6 +219,54 @@ class DGNPolicy(DQNPolicy):
         return np.asarray(gather, dtype=np.int64), np.asarray(segment, dtype=np.int64)
 
 
+class NDGNPolicy(DGNPolicy):
+    """Counterpart of policies/n_dgn.py:22-75 (the ``DGNPolicy`` of n_dgn_r.py / l_n_dgn_r.py / hl_n_dgn_r.py): the DGN-R loss with
+    each experience's siblings restricted to the agent itself and the neighbours its stored info reports active:
+
+        S_i   = { j : indices[i, j] >= 0 }  &  ( active_one_hop_neighbors[i] | {agent_id[i]} )       (n_dgn.py:36-47)
+        loss  = mean_i (returns_i - sum_{j in S_i} q_j)^2 * w   or   huber(sum_{j in S_i} q_j, returns_i)
+
+    ``learn`` / ``loss_backward`` take the dense form of :class:`DGNPolicy` with ``sibling`` = S_i as a [B, N] mask (what
+    :class:`melissa_amd.replay.NDGNLearner` samples; captured like DGN-R), the row form of :class:`DGNPolicy` (``segment``), or
+    the reference's layout: ``indices`` [B, N] (info.indices), ``active_one_hop_neighbors`` [B, N] bool, ``agent_id`` [B],
+    ``active_obs`` [M, 8N+1] with ``active_index`` [M] (active_obs.index; default: every valid entry of ``indices`` in row order,
+    as collaborative_shared_policy.py:55-59 gathers them) and ``active_act`` [M]."""
+
+    def loss_backward(self, batch) -> torch.Tensor:
+        if isinstance(batch, dict) and "obs_matrix" not in batch and "segment" not in batch:
+            indices = np.asarray(batch["indices"])
+            active_index = batch.get("active_index")            # (collaborative_shared_policy.py:55-59 stacks every valid index)
+            active_index = indices[indices >= 0] if active_index is None else active_index
+            gather, segment = self.segments_from_indices(indices, active_index,
+                                                         batch["active_one_hop_neighbors"], batch["agent_id"])
+            obs = torch.as_tensor(np.asarray(batch["active_obs"]) if not torch.is_tensor(batch["active_obs"]) else batch["active_obs"])
+            rows = dict(active_obs=obs[torch.from_numpy(gather).to(obs.device)],
+                        active_act=torch.as_tensor(np.asarray(batch["active_act"])[gather]),
+                        segment=torch.from_numpy(segment), returns=batch["returns"])
+            if batch.get("weight") is not None:
+                rows["weight"] = batch["weight"]
+            loss = super().loss_backward(rows)
+            batch["weight"] = rows["weight"]                    # prio-buffer hook, n_dgn.py:67
+            return loss
+        return super().loss_backward(batch)
+
+    @staticmethod
+    def neighbour_indices(indices: np.ndarray, active_one_hop_neighbors: np.ndarray, agent_id) -> np.ndarray:
+        """n_dgn.py:36-43: ``indices`` [B, N] with every sibling outside ``active_one_hop_neighbors | {agent_id}`` set to -1."""
+        indices = np.asarray(indices)
+        nb = np.array(active_one_hop_neighbors, dtype=np.bool_, copy=True).reshape(indices.shape)
+        nb[np.arange(len(nb)), np.asarray(agent_id).astype(np.int64).reshape(-1)] = True
+        return np.where(nb & (indices >= 0), indices, -1)
+
+    @staticmethod
+    def segments_from_indices(indices: np.ndarray, active_index: np.ndarray, active_one_hop_neighbors=None, agent_id=None):
+        """:meth:`DGNPolicy.segments_from_indices` over the siblings N-DGN keeps (:meth:`neighbour_indices`); without
+        ``active_one_hop_neighbors`` it is DGN-R's lookup."""
+        if active_one_hop_neighbors is not None:
+            indices = NDGNPolicy.neighbour_indices(indices, active_one_hop_neighbors, agent_id)
+        return DGNPolicy.segments_from_indices(indices, active_index)
+
+
 class MultiAgentSharedPolicy(nn.Module):
     """One shared policy for every agent id (shared_policy.py:14-31): ``forward`` returns the actions
     in the batch's original order, exactly what the reference's split / stitch produces."""
@@ -249,3 +297,10 @@ class MultiAgentSharedPolicy(nn.Module):
 
     def learn(self, batch, **kwargs):
         return self.policy.learn(batch, **kwargs)
+
+
+class MultiAgentCollaborativeSharedPolicy(MultiAgentSharedPolicy):
+    """collaborative_shared_policy.py:15 under the reference's name and constructor (``MultiAgentCollaborativeSharedPolicy(policy,
+    env)``, n_dgn_r.py:80).  The reference's ``process_fn`` gathers every sampled experience's sibling rows out of the replay
+    (``active_obs`` / ``.index`` / ``.act``) for the collective policies; here the device replay samples them itself
+    (:class:`melissa_amd.replay.DGNLearner` / :class:`melissa_amd.replay.NDGNLearner`), so what is left is the shared policy."""

@@ -17,7 +17,11 @@ from .optim import adam_step
 
 
 class RoundReplay:
-    def __init__(self, n_envs: int, n_nodes: int, capacity: int, device):
+    """``neighbours=True`` also records, for each acting agent, ``info['active_one_hop_neighbors']`` at its next observation
+    (``active_nb`` [B, K, N(, W)], N * W * 8 bytes per record): what the collective collector stores with every transition and
+    N-DGN restricts the sibling sum to (policies/n_dgn.py:36-47, :class:`NDGNLearner`)."""
+
+    def __init__(self, n_envs: int, n_nodes: int, capacity: int, device, neighbours: bool = False):
         self.B, self.n, self.K = n_envs, n_nodes, capacity
         dev = torch.device(device)
         self.obs = torch.zeros(n_envs, capacity, 8 * n_nodes, dtype=torch.float32, device=dev)
@@ -36,6 +40,10 @@ class RoundReplay:
         s.obs, s.obs_next = self.obs.data_ptr(), self.obs_next.data_ptr()
         s.acted, s.done, s.act = self.acted.data_ptr(), self.done.data_ptr(), self.act.data_ptr()
         s.rew, s.episode, s.cursor = self.rew.data_ptr(), self.episode.data_ptr(), self.cursor.data_ptr()
+        self.active_nb = None
+        if neighbours:
+            self.active_nb = torch.zeros(n_envs, capacity, n_nodes, *ws, dtype=torch.int64, device=dev)
+            s.active_nb = self.active_nb.data_ptr()
         self.struct = s
         node = torch.arange(n_nodes, device=dev)
         self._word, self._shift = node // 64, node % 64
@@ -57,6 +65,14 @@ class RoundReplay:
             m = m[..., None]
         return ((m.gather(-1, (agent // 64)[:, None]).squeeze(-1) >> (agent % 64)) & 1) != 0
 
+    def _bit(self, agent: torch.Tensor) -> torch.Tensor:
+        """agent [bs] -> node sets int64 [bs, (W)] holding just that agent."""
+        one = torch.ones_like(agent)
+        if self.W == 1:
+            return one << agent
+        return torch.where(agent[:, None] // 64 == torch.arange(self.W, device=agent.device)[None, :],
+                           one[:, None] << (agent % 64)[:, None], torch.zeros_like(agent)[:, None])
+
     def _popcount(self, m: torch.Tensor) -> torch.Tensor:
         return self._members(m).sum(-1)
 
@@ -67,7 +83,8 @@ class RoundReplay:
     def sample(self, batch_size: int, n_step: int, gamma: float, generator: torch.Generator | None = None):
         """Uniform over (record, acting agent) pairs.  Returns dict of device tensors:
         obs [bs, 8N+1], act [bs], ret [bs] (discounted n-step reward sum), boot_obs [bs, 8N+1] (observation to
-        bootstrap from), boot_w [bs] (gamma^steps, 0 when the agent terminated inside the window), env / slot / agent [bs].
+        bootstrap from), boot_w [bs] (gamma^steps, 0 when the agent terminated inside the window), env / slot / agent [bs];
+        with ``neighbours`` also nb_sibling [bs, (W)]: ``acted & (active_nb[agent] | agent)``, the siblings N-DGN sums over.
 
         On the GPU this is ONE launch (``mel_replay_sample``; the index arithmetic below is ~150 small launches, 0.6 ms of a
         1.7 ms update replayed from HIP graphs): draws are a counter-based function of the generator's seed and a device-side
@@ -108,8 +125,11 @@ class RoundReplay:
         idx_col = agent.float()[:, None]
         obs = torch.cat([self.obs[e, k], idx_col], dim=1)
         boot_obs = torch.cat([self.obs_next[e, boot_slot], idx_col], dim=1)
-        return dict(obs=obs, act=self.act[e, k, agent].long(), ret=ret, boot_obs=boot_obs, boot_w=boot_w,
-                    env=e, slot=k, agent=agent)
+        out = dict(obs=obs, act=self.act[e, k, agent].long(), ret=ret, boot_obs=boot_obs, boot_w=boot_w,
+                   env=e, slot=k, agent=agent)
+        if self.active_nb is not None:
+            out["nb_sibling"] = self.acted[e, k] & (self.active_nb[e, k, agent] | self._bit(agent))
+        return out
 
 
     def _sample_device(self, batch_size: int, n_step: int, gamma: float, generator):
@@ -128,6 +148,8 @@ class RoundReplay:
                    boot_w=torch.empty(batch_size, device=dev), env=torch.empty(batch_size, dtype=torch.int64, device=dev),
                    slot=torch.empty(batch_size, dtype=torch.int64, device=dev),
                    agent=torch.empty(batch_size, dtype=torch.int64, device=dev))
+        if self.active_nb is not None:
+            out["nb_sibling"] = torch.empty(batch_size, *self.acted.shape[2:], dtype=torch.int64, device=dev)
         b = _lib.MelReplayBatch()
         for name, t in out.items():
             setattr(b, name, t.data_ptr())
@@ -156,7 +178,9 @@ class RoundReplay:
         collective_experience_collector.py:70-80,251-309): one row per (record, acting agent) transition with
         ``buffer_id = env * N + agent`` (the Tianshou VectorReplayBuffer sub-buffer it is routed to) and
         ``indices`` [T, N]: row of each SIBLING transition (agent j acted in the same env round) or -1.
-        Rows are ordered by env, record age (oldest first), agent id.  Host NumPy; synchronises."""
+        Rows are ordered by env, record age (oldest first), agent id.  With ``neighbours``, ``active_one_hop_neighbors`` [T, N]
+        bool: the info of the agent's next observation, as the collective collector stores it (:270-290).  Host NumPy;
+        synchronises."""
         import numpy as np
         valid = self._valid_slots()
         B, K, n = self.B, self.K, self.n
@@ -177,6 +201,8 @@ class RoundReplay:
                    act=self.act[ee, kk, agent].long(), rew=self.rew[ee, kk], rew_agent=self.rew[ee, kk, agent],
                    done=self._has(self.done[ee, kk], agent), env_id=ee, agent_id=agent,
                    buffer_id=ee * n + agent, record_slot=kk, episode=self.episode[ee, kk].long(), indices=row_of[rec])
+        if self.active_nb is not None:
+            out["active_one_hop_neighbors"] = self._members(self.active_nb[ee, kk, agent])
         return {name: t.cpu().numpy() for name, t in out.items()}
 
 
@@ -324,7 +350,9 @@ class DGNLearner(DQNLearner):
     def sample_batch(self) -> dict:
         """Sample + n-step targets in the DENSE form (static shapes, no host synchronisation): obs_matrix [B, 8N], act_all
         [B, N], sibling [B, N] (the agents that acted in the sampled round), returns [B]."""
-        b = self.replay.sample(self.batch_size, self.n_step, self.gamma, self.gen)
+        return self._dense_batch(self.replay.sample(self.batch_size, self.n_step, self.gamma, self.gen))
+
+    def _dense_batch(self, b: dict) -> dict:
         e, k = b["env"], b["slot"]
         with torch.no_grad():
             target_net = self.policy.model_old if getattr(self.policy, "_target", False) else self.policy.model
@@ -353,3 +381,30 @@ class DGNLearner(DQNLearner):
         batch = self.sample_batch()
         self.last_batch = dict(batch, **self.row_form(batch))
         return self.policy.learn(dict(batch), grad_hook=self.grad_hook)
+
+
+class NDGNLearner(DGNLearner):
+    """N-DGN update (policies/n_dgn.py:22-75, policy = :class:`melissa_amd.policy.NDGNPolicy`): the DGN-R loss with each sampled
+    experience's siblings restricted to the agent itself and the one-hop neighbours its next observation reported active
+    (``info['active_one_hop_neighbors']``).  Needs a ``RoundReplay(neighbours=True)``; the sampler returns the restricted set
+    (``nb_sibling``), so the dense form keeps static shapes and ``capture()`` replays it from HIP graphs.  Targets are DGN-R's:
+    ``ret + boot_w * best``.  ``row_form`` (inherited) only when a caller asks for it."""
+
+    def __init__(self, policy, replay: RoundReplay, *args, **kwargs):
+        if replay.active_nb is None:
+            raise ValueError("NDGNLearner needs a RoundReplay(neighbours=True): N-DGN restricts the siblings to active_nb")
+        super().__init__(policy, replay, *args, **kwargs)
+
+    def sample_batch(self) -> dict:
+        """Like :meth:`DGNLearner.sample_batch`, with ``sibling`` [B, N] = the restricted set ``nb_sibling``."""
+        b = self.replay.sample(self.batch_size, self.n_step, self.gamma, self.gen)
+        out = self._dense_batch(b)
+        out["sibling"] = self.replay._members(b["nb_sibling"])
+        out["agent"] = b["agent"]
+        return out
+
+    def step(self) -> dict:
+        if self.captured is not None:
+            return self.captured.step()
+        self.last_batch = self.sample_batch()
+        return self.policy.learn(dict(self.last_batch), grad_hook=self.grad_hook)

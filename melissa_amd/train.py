@@ -19,9 +19,15 @@ import time
 # parses its arguments, starts the ranks and never gets as far as ``train()``.
 
 
+MODELS = ("l_dgn", "hl_dgn", "dgn_r", "n_dgn_r", "l_n_dgn_r", "hl_n_dgn_r")       # the reference's args.algorithm names
+# N-DGN (policies/n_dgn.py): n_dgn_r.py / l_n_dgn_r.py / hl_n_dgn_r.py train DGN-R / L-DGN / HL-DGN networks with it
+N_DGN_NETWORK = {"n_dgn_r": "dgn_r", "l_n_dgn_r": "l_dgn", "hl_n_dgn_r": "hl_dgn"}
+
+
 def build_network(name: str, n_nodes: int, device, hidden=128, heads=4):
     from .networks import DGNRNetwork, HLDGNNetwork, LDGNNetwork
     duel = ({"hidden_sizes": [128, 128]}, {"hidden_sizes": [128, 128]})          # common.py:41-42
+    name = N_DGN_NETWORK.get(name, name)
     if name == "l_dgn":
         return LDGNNetwork(5, hidden, 2, heads, n_nodes, dueling_param=duel, device=device)
     if name == "hl_dgn":
@@ -29,6 +35,21 @@ def build_network(name: str, n_nodes: int, device, hidden=128, heads=4):
     if name == "dgn_r":
         return DGNRNetwork(5, hidden, 2, heads, n_nodes, dueling_param=duel, device=device)
     raise ValueError(name)
+
+
+def policy_and_learner(name: str):
+    """(policy class, learner class, replay records neighbours) of a model name: dgn_r.py trains with DGNPolicy (summed sibling
+    Q, policies/dgn.py), the three N scripts with N-DGN (policies/n_dgn.py, siblings restricted to the one-hop neighbours),
+    l_dgn.py / hl_dgn.py with DQNPolicy."""
+    from .policy import DGNPolicy, DQNPolicy, NDGNPolicy
+    from .replay import DGNLearner, DQNLearner, NDGNLearner
+    if name not in MODELS:
+        raise ValueError(name)
+    if name in N_DGN_NETWORK:
+        return NDGNPolicy, NDGNLearner, True
+    if name == "dgn_r":
+        return DGNPolicy, DGNLearner, False
+    return DQNPolicy, DQNLearner, False
 
 
 def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4, batch_size=32, n_step=4,
@@ -39,15 +60,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
     pools >= 4096 go through the on-disk packed cache, ``melissa_amd.env.cached_graph_pool``).  Episodes come from the
     device episode stream: every reset draws a new (graph, source, interested set, movement seed) like World.reset.
-    ``capture_updates``: replay the update from HIP graphs (``DQNLearner.capture``; DGN-R too: its dense sibling form has static
-    shapes, replay.DGNLearner).  None = on unless a probe is attached; with several ranks the collective stays
+    ``capture_updates``: replay the update from HIP graphs (``DQNLearner.capture``; DGN-R and N-DGN too: their dense sibling forms
+    have static shapes, replay.DGNLearner / replay.NDGNLearner).  None = on unless a probe is attached; with several ranks the collective stays
     eager between two graphs.  The capture takes two extra (real, untimed) updates first: ``warmup_updates`` in the result."""
     import torch
     from . import launch, parallel
     from .collect import RoundLoop
     from .env import HipGraphVectorEnv, synthetic_graph_pool
-    from .policy import DGNPolicy, DQNPolicy
-    from .replay import DGNLearner, DQNLearner, RoundReplay
+    from .replay import RoundReplay
     if backend != "gloo":
         launch.check_rank_device()                             # exit 2 when LOCAL_RANK names a GPU this rank cannot see
     rank, local_rank, world = parallel.init_distributed(backend)
@@ -56,15 +76,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     torch.manual_seed(seed)                                    # same init everywhere, then broadcast anyway
     net = build_network(model, n_nodes, device)
     parallel.broadcast_parameters(net, src=0)
-    # dgn_r.py trains with DGNPolicy (summed sibling Q, policies/dgn.py); l_dgn.py / hl_dgn.py with DQNPolicy
-    policy_cls, learner_cls = (DGNPolicy, DGNLearner) if model == "dgn_r" else (DQNPolicy, DQNLearner)
+    policy_cls, learner_cls, neighbours = policy_and_learner(model)
     policy = policy_cls(net, torch.optim.Adam(net.parameters(), lr=lr), discount_factor=gamma,
                         estimation_step=n_step, target_update_freq=target_update_freq)
     from .env import cached_graph_pool
     graph_list = cached_graph_pool(n_nodes, graphs, 0) if graphs >= 4096 else synthetic_graph_pool(n_nodes, graphs, first_seed=0)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False)
-    replay = RoundReplay(envs, n_nodes, replay_rounds, device)
+    replay = RoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours)
     # the rounds between two updates replay from one HIP graph (bit-identical to the eager launches: tests/test_gpu_round.py)
     loop = RoundLoop(venv, policy, seed=1000 + rank * envs, eps=eps, replay=replay, ring=ring,
                      use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update))
@@ -114,7 +133,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="hl_dgn", choices=["l_dgn", "hl_dgn", "dgn_r"])
+    ap.add_argument("--model", default="hl_dgn", choices=list(MODELS))
     ap.add_argument("--nodes", type=int, default=20)
     ap.add_argument("--envs", type=int, default=256, help="envs per GPU")
     ap.add_argument("--updates", type=int, default=20)
