@@ -442,6 +442,11 @@ typedef struct mel_env_batch {
     uint64_t* plan_u1;         /* [B]   */
     uint64_t* plan_u2;         /* [B]   */
     int32_t*  plan_cnt;        /* [3*B] */
+    /* State.received_from (core.py:22,276-278) as node sets: node i's set holds every node it has received the message
+     * from this episode.  Carved by mel_env_bind behind every other field; read and written only when heuristic ==
+     * MEL_HEURISTIC_MPR (rule core.py:236-243 is the only reader).  Empty at each reset, then set by the reset's own
+     * World.step (core.py:437). */
+    uint64_t* received_from;   /* [B, N]    */
 } mel_env_batch;
 
 /* An episode pool: what World.reset samples (core.py:372-394), pre-drawn on the host with the
@@ -531,13 +536,22 @@ mel_status mel_wait_counter(const uint32_t* counter, uint32_t target, uint32_t t
 mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool* graphs, const mel_episode_pool* pool,
                               const mel_env_batch* env, int32_t max_new, int32_t discard, void* stream);
 
-/* Scripted agents (scripted_agents_ratio > 0): the deterministic heuristics of
- * graph_env/env/utils/heuristics/core.py.  The probabilistic ones (probabilistic_gossip / _relay) draw from the
- * process-global np.random and "mpr" does not return a HeuristicResult: not offered. */
+/* Scripted agents (scripted_agents_ratio > 0): the deterministic heuristics of graph_env/env/utils/heuristics/.  The
+ * probabilistic ones (probabilistic_gossip / _relay) draw from the process-global np.random: not offered. */
 #define MEL_HEURISTIC_NONE                  0
 #define MEL_HEURISTIC_SIMPLE_BROADCAST      1   /* action = 0 if has_taken_action else 1     heuristics/core.py:13-18 */
 #define MEL_HEURISTIC_BROADCAST_IF_INTERESTED 2 /* action = number_interested_neighbors > 0  :45-53 */
 #define MEL_HEURISTIC_SILENT                3   /* action = 0                                :56-62 */
+/* OLSR multipoint relays (RFC 3626), heuristics/mpr.py:7-72.  mpr_heuristic returns a bare array where World.step reads
+ * a HeuristicResult (core.py:227-234); it is read as HeuristicResult(relay_mask=mpr, action=None): every scripted agent
+ * names its MPR set at every world step, a scripted node that some scripted neighbour chose forwards once, and only
+ * after receiving the message from one of those neighbours (core.py:236-243).  Uses mel_env_batch.received_from. */
+#define MEL_HEURISTIC_MPR                   4
+
+/* The MPR set (MEL_HEURISTIC_MPR's selection) of every node of n_graphs undirected graphs of n_nodes <= MEL_MAX_NODES
+ * nodes: one_hop device uint64 [G, N, MEL_SET_WORDS(N)] adjacency node sets (symmetric, no self loops - not checked
+ * here), mpr_out the same shape.  The device function the env kernels run. */
+mel_status mel_mpr_sets(const uint64_t* one_hop, int32_t n_graphs, int32_t n_nodes, uint64_t* mpr_out, void* stream);
 
 /* Outputs of last() + [3P] PettingZooEnv packing, one row per listed env (device; any may be NULL). */
 typedef struct mel_env_obs {

@@ -40,11 +40,11 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
-           "mel_prof_read", "mel_last_error", "mel_version")
+           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
-HEURISTICS = {None: 0, "simple_broadcast": 1, "broadcast_if_any_interested": 2, "silent": 3}
+HEURISTICS = {None: 0, "simple_broadcast": 1, "broadcast_if_any_interested": 2, "silent": 3, "mpr": 4}
 LOGGER_KEYS = ("total_messages_transmitted", "coverage", "messages_sent", "messages_received", "n_neighbours",
                "interested_agents", "coverage_interested_fraction", "coverage_interested_count",
                "uninterested_with_message", "episode_rewards_sum")      # graph.py:166-178
@@ -113,7 +113,7 @@ class MelEnvBatch(C.Structure):
                 ("log_capacity", C.c_int32), ("log_reserved", C.c_int32), ("log_cursor", C.c_void_p),
                 ("log_stats", C.c_void_p), ("log_meta", C.c_void_p),
                 ("plan_adj", C.c_void_p), ("plan_live", C.c_void_p), ("plan_u1", C.c_void_p), ("plan_u2", C.c_void_p),
-                ("plan_cnt", C.c_void_p)]
+                ("plan_cnt", C.c_void_p), ("received_from", C.c_void_p)]
 
 
 class MelEpisodePool(C.Structure):
@@ -245,6 +245,8 @@ def load(build_if_missing: bool = True):
                                       C.POINTER(MelReplayBatch), vp]
     lib.mel_env_observe.restype = i32
     lib.mel_env_observe.argtypes = [E, vp, i64, O, vp]
+    lib.mel_mpr_sets.restype = i32
+    lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz
     lib.mel_feature_tables_bytes.argtypes = [W, i32]
     lib.mel_prepare_feature_tables.restype = i32

@@ -13,7 +13,7 @@
 //   World.step / relay_message / move_graph / update_*_hop / reset       graph_env/env/utils/core.py:225-437
 //   CustomSelector                                                       graph_env/env/utils/selector.py
 //   [3P] AECEnv._deads_step_first / _was_dead_step, tianshou PettingZooEnv.step
-// Scripted agents run the deterministic heuristics of heuristics/core.py (MEL_HEURISTIC_*).
+// Scripted agents run the deterministic heuristics of heuristics/core.py and mpr.py (MEL_HEURISTIC_*).
 #include "common.hpp"
 #include "plan_masks.hpp"
 
@@ -112,26 +112,118 @@ __device__ __forceinline__ void env_store(const mel_env_batch& e, int b, int lan
     }
 }
 
+// One node set per node in LDS, this wavefront's slot of the 256-thread workgroup (two_hop_of, mpr_of: one array for both)
+template <int W>
+__device__ __forceinline__ uint64_t (&node_rows())[64 * W][W] {
+    __shared__ uint64_t rows[4][64 * W][W];
+    return rows[(threadIdx.x >> 6) & 3];
+}
+
 // core.py:334-341: one-hop OR neighbours' one-hop, minus self
 template <int W>
 __device__ __forceinline__ void two_hop_of(const NodeSet<W> (&one_hop)[W], int lane, int n, NodeSet<W> (&two_hop)[W]) {
     // every lane walks ITS OWN neighbours (a handful, not all n nodes) and ORs their rows in, fetched from LDS by a
     // per-lane gather; the wave iterates max-degree times instead of n times with two v_readlane each
-    __shared__ uint64_t rows[4][64 * W][W];
-    const int w = (threadIdx.x >> 6) & 3;
+    uint64_t (&rows)[64 * W][W] = node_rows<W>();
     (void)n;
-    MEL_W_FOR(h) MEL_W_FOR(k) rows[w][lane + 64 * h][k] = one_hop[h].w[k];          // (nodes >= n hold 0)
+    MEL_W_FOR(h) MEL_W_FOR(k) rows[lane + 64 * h][k] = one_hop[h].w[k];          // (nodes >= n hold 0)
     MEL_W_FOR(h) {
         NodeSet<W> m = one_hop[h], rest = one_hop[h];
         while (__ballot(ns_any(rest))) {
             if (ns_any(rest)) {
                 const int j = ns_lowest(rest);
                 ns_clear_lowest(rest);
-                MEL_W_FOR(k) m.w[k] |= rows[w][j][k];
+                MEL_W_FOR(k) m.w[k] |= rows[j][k];
             }
         }
         two_hop[h] = m & ~ns_bit<W>(lane + 64 * h);
     }
+}
+
+// OLSR multipoint relays (RFC 3626) as heuristics/mpr.py:7-72 selects them, for each node lane + 64 h with want[h] (the
+// other mpr[h] are empty).  N1 = one_hop, N2 = two-hop minus N1 (mpr.py:18); the whole wave takes part (it writes the
+// rows), each lane walks only its own neighbours and reads their rows from LDS, as two_hop_of does.
+//   (1) every node of N2 that exactly one neighbour reaches makes that neighbour a relay and counts as covered (:43-47) -
+//       only those nodes, not all that the chosen relays reach, so (2) may pick a relay that is already in the set;
+//   (2) while N2 has uncovered nodes: the neighbour that reaches most of them becomes a relay, the largest id among
+//       equals (max(dict), :60-66; the d_y degrees are never compared), and what it reaches counts as covered.
+// Every node of N2 has a neighbour that reaches it, so each pick covers one node at least: at most |N2| picks.
+template <int W>
+__device__ __forceinline__ void mpr_of(const NodeSet<W> (&one_hop)[W], const bool (&want)[W], int lane,
+                                       NodeSet<W> (&mpr)[W]) {
+    uint64_t (&rows)[64 * W][W] = node_rows<W>();
+    MEL_W_FOR(h) MEL_W_FOR(k) rows[lane + 64 * h][k] = one_hop[h].w[k];
+    MEL_W_FOR(h) {
+        const NodeSet<W> n1 = want[h] ? one_hop[h] : ns_zero<W>();
+        NodeSet<W> once = ns_zero<W>(), twice = ns_zero<W>(), rest = n1, row;
+        while (ns_any(rest)) {                                   // nodes reached by one / by two or more neighbours
+            const int u = ns_lowest(rest);
+            ns_clear_lowest(rest);
+            MEL_W_FOR(k) row.w[k] = rows[u][k];
+            twice |= once & row;
+            once |= row;
+        }
+        const NodeSet<W> n2 = once & ~n1 & ~ns_bit<W>(lane + 64 * h);
+        const NodeSet<W> unique = n2 & ~twice;
+        NodeSet<W> m = ns_zero<W>();
+        rest = ns_any(unique) ? n1 : ns_zero<W>();
+        while (ns_any(rest)) {                                   // (1)
+            const int u = ns_lowest(rest);
+            ns_clear_lowest(rest);
+            MEL_W_FOR(k) row.w[k] = rows[u][k];
+            if (ns_any(row & unique)) m |= ns_bit<W>(u);
+        }
+        NodeSet<W> left = n2 & ~unique;
+        for (int picks = ns_count(left); picks > 0 && ns_any(left); --picks) {     // (2)
+            int best = -1, best_count = 1;
+            NodeSet<W> best_row = ns_zero<W>();
+            rest = n1;
+            while (ns_any(rest)) {
+                const int u = ns_lowest(rest);
+                ns_clear_lowest(rest);
+                MEL_W_FOR(k) row.w[k] = rows[u][k];
+                const int c = ns_count(row & left);
+                if (c >= best_count) best = u, best_count = c, best_row = row;
+            }
+            if (best < 0) break;
+            m |= ns_bit<W>(best);
+            left &= ~best_row;
+        }
+        mpr[h] = m;
+    }
+}
+
+// World.step with MEL_HEURISTIC_MPR, before the relay loop (core.py:226-243): every scripted agent a names its MPR set M(a)
+// and becomes a relayed-for node of each member (relays_for[b] |= {a}, :229-231; the action stays as it is).  A scripted
+// node b that some scripted neighbour chose then transmits iff it has not transmitted yet, holds the message (or is the
+// source) and has received it from one of those neighbours (or is the source); it stays silent otherwise (:236-243).
+// relays_for is the transpose of the M rows: M(a) lies in a's one-hop set and graphs are undirected, so lane b walks its
+// scripted neighbours and reads their rows from LDS.  On return the LDS rows hold State.received_from of every node for
+// the relay loop to extend (no registers stay reserved for it across the loop): empty in the reset's own World.step (the
+// one that starts with no message transmitted, core.py:389,437; State.reset :21-22), else what the episode recorded.
+template <int W>
+__device__ __forceinline__ void mpr_relay_rule(const mel_env_batch& e, int b, Env<W>& s, const bool (&scripted_lane)[W],
+                                               int lane) {
+    const int n = e.n_nodes;
+    NodeSet<W> m[W], rf[W];
+    mpr_of<W>(s.one_hop, scripted_lane, lane, m);
+    uint64_t (&rows)[64 * W][W] = node_rows<W>();
+    MEL_W_FOR(h) MEL_W_FOR(k) rows[lane + 64 * h][k] = m[h].w[k];
+    MEL_W_FOR(h) {
+        rf[h] = (s.world_msgs == 0 || lane + 64 * h >= n) ? ns_zero<W>() : ns_load<W>(e.received_from, (size_t)b * n + lane + 64 * h);
+        NodeSet<W> relays_for = ns_zero<W>(), rest = scripted_lane[h] ? (s.one_hop[h] & s.scripted) : ns_zero<W>();
+        while (ns_any(rest)) {
+            const int a = ns_lowest(rest);
+            ns_clear_lowest(rest);
+            if ((rows[a][h] >> lane) & 1ull) relays_for |= ns_bit<W>(a);      // node lane + 64 h: word h, bit lane
+        }
+        if (ns_any(relays_for)) {
+            const bool origin = ns_mine(s.origin_set, lane, h);
+            s.act[h] = (!ns_mine(s.taken_action, lane, h) && (ns_mine(s.has_msg, lane, h) || origin) &&
+                        (ns_any(rf[h] & relays_for) || origin)) ? 1 : 0;
+        }
+    }
+    MEL_W_FOR(h) MEL_W_FOR(k) rows[lane + 64 * h][k] = rf[h].w[k];
 }
 
 // nx.geometric_edges (core.py:311): edge iff dx*dx + dy*dy <= 0.2**2 in float64.
@@ -188,15 +280,15 @@ __device__ unsigned long long g_world_prof[4];
 
 // World.step core.py:225-266
 template <int W>
-__device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_episode_pool& pool, Env<W>& s,
+__device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_episode_pool& pool, int b, Env<W>& s,
                                            int lane) {
     const int n = e.n_nodes;
 #ifdef MEL_ENV_PROF
     const unsigned long long wp0 = __builtin_readcyclecounter();
 #endif
     s.info_valid_cache = 0;                                  // message counters, coverage and (dynamic graph) degrees change here
-    // :226-234 scripted agents: action = heuristic(agent) (the heuristics offered return no relay mask, so the
-    // relays_for pass :236-243 never fires)
+    // :226-234 scripted agents: action = heuristic(agent) (only mpr returns a relay mask: the relays_for pass :236-243
+    // runs with it alone)
     // (no heuristic: Agent.action_callback stays None, World.scripted_agents is empty, nothing is overridden)
     bool scripted_lane[W];
     MEL_W_FOR(h) {
@@ -208,9 +300,11 @@ __device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_epi
             // first move and tracks the current graph afterwards (one_hop changes only in moves)
             else if (e.heuristic == MEL_HEURISTIC_BROADCAST_IF_INTERESTED)
                 s.act[h] = (e.dynamic_graph && s.move_cursor > 0 && ns_any(s.one_hop[h] & s.interested)) ? 1 : 0;
-            else s.act[h] = 0;                                       // silent
+            else if (e.heuristic == MEL_HEURISTIC_SILENT) s.act[h] = 0;
+            // (mpr: the action is None, nothing is overwritten)
         }
     }
+    if (e.heuristic == MEL_HEURISTIC_MPR) mpr_relay_rule<W>(e, b, s, scripted_lane, lane);
     // :246 the source always transmits on its first opportunity
     const int origin_msgs = node_i32<W>(s.msgs, s.origin);
     MEL_W_FOR(h) if (lane + 64 * h == s.origin && origin_msgs == 0) s.act[h] = 1;
@@ -227,8 +321,12 @@ __device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_epi
             s.taken_action |= ns_bit<W>(i);
             MEL_W_FOR(h) s.received[h] += (int)ns_mine(nb, lane, h);
             s.has_msg |= nb;
+            if (e.heuristic == MEL_HEURISTIC_MPR)                  // :276-277 received_from[j] |= {i} (LDS rows, mpr_relay_rule)
+                MEL_W_FOR(h) if (ns_mine(nb, lane, h)) node_rows<W>()[lane + 64 * h][i >> 6] |= 1ull << (i & 63);
         }
     }
+    if (e.heuristic == MEL_HEURISTIC_MPR)
+        MEL_W_FOR(h) if (lane + 64 * h < n) MEL_W_FOR(k) e.received_from[((size_t)b * n + lane + 64 * h) * W + k] = node_rows<W>()[lane + 64 * h][k];
 #ifdef MEL_ENV_PROF
     asm volatile("s_nop 0" ::"s"(s.has_msg.w[0]), "v"(s.received[0]));
     const unsigned long long wp1 = __builtin_readcyclecounter();
@@ -414,7 +512,7 @@ __device__ __forceinline__ bool env_step(const mel_env_batch& e, const mel_episo
                 if (ns_mine(s.alive, lane, h)) s.reward[h] = 0.0;       // _clear_rewards
                 s.act[h] = s.cur_act[h];                                // :362-365
             }
-            world_step(e, pool, s, lane);
+            world_step(e, pool, b, s, lane);
             write_obs_matrix(e, b, s, lane, obs_next_copy);             // :370-371
             double r[W];
             MEL_W_FOR(h) {
@@ -488,7 +586,7 @@ __device__ __forceinline__ void env_reset(const mel_env_batch& e, const mel_epis
         s.act[h] = NONE;
         s.steps[h] = (lane + 64 * h == s.origin) ? 1 : 0;               // :424,435
     }
-    world_step(e, pool, s, lane);                                       // :437
+    world_step(e, pool, b, s, lane);                                    // :437 (received_from starts empty here)
     // GraphEnv.reset
     MEL_W_FOR(h) {
         s.sel_steps[h] = (lane + 64 * h == s.origin) ? 1 : 0;           // selector.reinit + enable(on_reset)
@@ -579,6 +677,10 @@ struct RoundArgs {
 template <int W>
 __device__ __forceinline__ void env_reset_from_snapshot(const mel_env_batch& e, const mel_env_batch& snap, int b, Env<W>& s,
                                                         int episode, int lane) {
+    if (e.heuristic == MEL_HEURISTIC_MPR)                  // State.received_from after the reset's World.step
+        MEL_W_FOR(h) if (lane + 64 * h < e.n_nodes)
+            ns_store<W>(e.received_from, (size_t)b * e.n_nodes + lane + 64 * h,
+                        ns_load<W>(snap.received_from, (size_t)episode * e.n_nodes + lane + 64 * h));
     Env<W> t;
     env_load(snap, episode, lane, t);
     t.new_round = s.new_round, t.decisions = s.decisions, t.episodes_done = s.episodes_done;
@@ -840,6 +942,22 @@ __global__ __launch_bounds__(256) void env_kernel(StepArgs a) {
     env_store(a.env, b, lane, s);
 }
 
+// mel_mpr_sets: one wavefront per graph, the env kernels' MPR selection (mpr_of) for every node
+template <int W>
+__global__ __launch_bounds__(256) void mpr_sets_kernel(const uint64_t* one_hop, int n_graphs, int n, uint64_t* out) {
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= n_graphs) return;
+    const int lane = lane_id();
+    NodeSet<W> hop[W], m[W];
+    bool on[W];
+    MEL_W_FOR(h) {
+        on[h] = lane + 64 * h < n;
+        hop[h] = on[h] ? (ns_load<W>(one_hop, (size_t)g * n + lane + 64 * h) & ns_full<W>(n)) : ns_zero<W>();
+    }
+    mpr_of<W>(hop, on, lane, m);
+    MEL_W_FOR(h) if (on[h]) ns_store<W>(out, (size_t)g * n + lane + 64 * h, m[h]);
+}
+
 static mel_status check_env(const mel_env_batch* env, int64_t n) {
     if (!env) return fail(MEL_ERR_INVALID_ARG, "env batch is null");
     if (env->n_nodes < 1 || env->n_nodes > MEL_MAX_NODES) return fail(MEL_ERR_INVALID_ARG, "n_nodes=%d outside [1, %d]", env->n_nodes, MEL_MAX_NODES);
@@ -887,6 +1005,7 @@ static EnvLayout carve_env(int32_t B, int32_t n, void* state) {
     L.e.episode_rewards = c.take<double>(B);
     L.e.obs_matrix = c.take<float>(BN * 8);
     L.e.info_stats = c.take<double>(BN * MEL_ENV_LOGGER_STATS);
+    L.e.received_from = c.take<uint64_t>(BN * SW);     // last: the offsets above do not depend on it
     L.bytes = c.off;
     return L;
 }
@@ -912,7 +1031,7 @@ mel_status mel_env_bind(mel_env_batch* env, int32_t n_envs, int32_t n_nodes, voi
     const int32_t dyn = env->dynamic_graph, hlr = env->has_local_ratio, heu = env->heuristic, tst = env->is_testing;
     const double lr = env->local_ratio;
     const mel_env_batch keep = *env;               // the caller-owned episode log survives a (re)bind
-    if (heu < MEL_HEURISTIC_NONE || heu > MEL_HEURISTIC_SILENT) return fail(MEL_ERR_INVALID_ARG, "heuristic %d", heu);
+    if (heu < MEL_HEURISTIC_NONE || heu > MEL_HEURISTIC_MPR) return fail(MEL_ERR_INVALID_ARG, "heuristic %d", heu);
     *env = L.e;
     env->dynamic_graph = dyn, env->has_local_ratio = hlr, env->local_ratio = lr, env->heuristic = heu, env->is_testing = tst;
     env->log_capacity = keep.log_capacity, env->log_cursor = keep.log_cursor, env->log_stats = keep.log_stats,
@@ -1187,6 +1306,18 @@ void mel_debug_env_prof(unsigned long long* out9) {
 #else
     for (int i = 0; i < 9; ++i) out9[i] = 0;
 #endif
+}
+
+mel_status mel_mpr_sets(const uint64_t* one_hop, int32_t n_graphs, int32_t n_nodes, uint64_t* mpr_out, void* stream) {
+    if (!one_hop || !mpr_out) return fail(MEL_ERR_INVALID_ARG, "mel_mpr_sets: null argument");
+    if (n_graphs < 0 || n_nodes < 1 || n_nodes > MEL_MAX_NODES)
+        return fail(MEL_ERR_INVALID_ARG, "mel_mpr_sets: n_graphs=%d n_nodes=%d (nodes in [1, %d])", n_graphs, n_nodes, MEL_MAX_NODES);
+    if (n_graphs == 0) return MEL_OK;
+    clear_stale_error();
+    const dim3 grid((unsigned)(((int64_t)n_graphs + 3) / 4));
+    if (n_nodes > 64) MEL_LAUNCH(mpr_sets_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), one_hop, n_graphs, n_nodes, mpr_out);
+    else MEL_LAUNCH(mpr_sets_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), one_hop, n_graphs, n_nodes, mpr_out);
+    return check_launch("mpr_sets");
 }
 
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n, const mel_env_obs* out,

@@ -25,6 +25,39 @@ LOGGER_KEYS = ("total_messages_transmitted", "coverage", "messages_sent", "messa
                "uninterested_with_message", "episode_rewards_sum")          # graph.py:167-177
 
 
+def mpr_sets(one_hop: torch.Tensor) -> torch.Tensor:
+    """OLSR multipoint relay sets (RFC 3626 as heuristics/mpr.py:7-72 selects them) of every node of a batch of undirected
+    graphs, computed by the env kernels' own device function (mel_mpr_sets).
+
+    ``one_hop``: device int64 adjacency node sets, ``[G, N]`` for N <= 64 or ``[G, N, 2]`` for 64 < N <= 128 (bit j of row i:
+    edge i-j; word k holds nodes 64 k .. 64 k + 63).  Returns the same shape: bit u of row v = u is one of v's relays.
+    Raises ValueError on an asymmetric adjacency, a self loop or a bit beyond node N - 1."""
+    if not isinstance(one_hop, torch.Tensor) or one_hop.dtype != torch.int64 or one_hop.dim() not in (2, 3):
+        raise ValueError("mpr_sets: one_hop must be an int64 tensor [G, N] or [G, N, 2]")
+    g, n = int(one_hop.shape[0]), int(one_hop.shape[1])
+    _lib.check_n_nodes(n, "mpr_sets")
+    if tuple(one_hop.shape[2:]) != set_shape(n):
+        raise ValueError(f"mpr_sets: {n} nodes need node sets of shape {set_shape(n)}, got {tuple(one_hop.shape[2:])}")
+    words = one_hop.reshape(g, n, -1)
+    bits = ((words[:, :, :, None] >> torch.arange(64, device=one_hop.device)) & 1).reshape(g, n, -1).bool()
+    if bool(bits[:, :, n:].any()):
+        raise ValueError(f"mpr_sets: adjacency rows name nodes beyond {n - 1}")
+    adj = bits[:, :, :n]                                                      # [G, N, N]
+    if bool(adj.diagonal(dim1=1, dim2=2).any()):
+        raise ValueError("mpr_sets: the adjacency has self loops")
+    if not bool(torch.equal(adj, adj.transpose(1, 2))):
+        raise ValueError("mpr_sets: the adjacency is not symmetric (graphs are undirected)")
+    if one_hop.device.type != "cuda":
+        raise ValueError("mpr_sets: one_hop must be a device tensor")
+    src = one_hop.contiguous()
+    out = torch.empty_like(src)
+    lib = _lib.load()
+    with torch.cuda.device(src.device):
+        _lib.check(lib.mel_mpr_sets(src.data_ptr(), g, n, out.data_ptr(), _lib.current_stream_ptr(src.device)),
+                   "mel_mpr_sets")
+    return out
+
+
 class Discrete:
     """Minimal gym ``Discrete(n)`` stand-in for ``action_space`` (graph.py:103)."""
 
@@ -279,6 +312,17 @@ class HipGraphVectorEnv:
 
     def two_hop(self):
         return self._field(self.env.two_hop, self.n * set_words(self.n), torch.int64).view(self.env_num, self.n, *set_shape(self.n))
+
+    def received_from(self):
+        """[B, N] int64 bit patterns ([B, N, W] beyond 64 nodes): State.received_from of every node (core.py:276-278), kept
+        with the "mpr" heuristic only (the other configurations leave it zero)."""
+        return self._field(self.env.received_from, self.n * set_words(self.n), torch.int64).view(self.env_num, self.n,
+                                                                                                 *set_shape(self.n))
+
+    def mpr_sets(self) -> torch.Tensor:
+        """The MPR set (heuristics/mpr.py) of every node of the graph each env holds now: int64 [B, N] ([B, N, W] beyond 64
+        nodes), see :func:`mpr_sets`."""
+        return mpr_sets(self.one_hop())
 
     # ------------------------------------------------------------------ reset / step
     def _reset_rows(self, ids: np.ndarray, observe: bool = True):

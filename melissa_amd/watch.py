@@ -2,10 +2,13 @@
 run test episodes on evaluation envs, report the episodes' statistics).
 
     python -m melissa_amd.watch --model l_dgn --nodes 20 --envs 1 --episodes 10 [--load policy.pth]
+                                [--heuristic mpr --scripted-agents-ratio 0.5]
 
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
 ``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by the reference's trainer (keys ``model.*`` /
-``model_old.*``, l_dgn.py:311), loaded with ``weights_only=True``.
+``model_old.*``, l_dgn.py:311), loaded with ``weights_only=True``.  ``--heuristic`` / ``--scripted-agents-ratio`` are the
+reference's flags (common.py:67,69): that fraction of the nodes runs the heuristic instead of the policy (in the evaluation
+schedule the policy still decides for them, graph.py:244,340; the heuristic overrides it inside the world step).
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ from .train import build_network
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
-          dynamic_graph=True, feature_dtype="f32"):
+          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0):
     torch.manual_seed(seed)
     net = build_network(model, n_nodes, device)
     policy = DQNPolicy(net, target_update_freq=1)
@@ -31,7 +34,8 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     net.set_feature_dtype(feature_dtype)
     pool = graph_pool if graph_pool is not None else synthetic_graph_pool(n_nodes, 16, first_seed=0)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=pool, dynamic_graph=dynamic_graph, device=device, max_moves=64,
-                             seed=seed, construct_like_reference=False, is_testing=True, num_test_episodes=episodes)
+                             seed=seed, construct_like_reference=False, is_testing=True, num_test_episodes=episodes,
+                             scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic)
     per_env = -(-episodes // envs) + 2
     col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64)
     out = col.collect(n_episode=episodes)
@@ -41,7 +45,7 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     return {k: out[k] for k in keys}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="l_dgn", choices=["l_dgn", "hl_dgn", "dgn_r"])
     ap.add_argument("--nodes", type=int, default=20)
@@ -49,8 +53,13 @@ def main():
     ap.add_argument("--episodes", type=int, default=10)
     ap.add_argument("--load", default=None)
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f32s", "f32a"])
-    a = ap.parse_args()
-    print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype)))
+    ap.add_argument("--heuristic", default=None, choices=["simple_broadcast", "broadcast_if_any_interested", "silent", "mpr"],
+                    help="heuristic the scripted agents run (common.py:67)")
+    ap.add_argument("--scripted-agents-ratio", type=float, default=0.0,
+                    help="fraction of the nodes that are scripted agents (common.py:69)")
+    a = ap.parse_args(argv)
+    print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype, heuristic=a.heuristic,
+                           scripted_agents_ratio=a.scripted_agents_ratio)))
 
 
 if __name__ == "__main__":
