@@ -227,11 +227,27 @@ mel_status mel_hldgn_forward(const mel_weights* w, int32_t aggregator, const flo
                              int32_t n_nodes, int32_t obs_width, float* logits, void* workspace,
                              size_t ws_bytes, void* stream);
 
+/* Tile codes of mel_gemm_f32, mel_gemm_f32_split and mel_gemm_bf16 (the `tile` argument), per entry point:
+ *   MEL_TILE_AUTO            all three: the library's choice
+ *   MEL_TILE_64              f32, f32_split: 64 x 64 workgroup tiles
+ *   MEL_TILE_128             all three: 128 x 128 tiles (N % 128 == 0; f32 and bf16 choose automatically otherwise)
+ *   MEL_TILE_WIDE            f32_split: 128 x 256 tiles with both operands as bf16 plane blocks (gemm_planes_kernel);
+ *                            bf16: 128 x 256 tiles (gemm_bf16_wide_kernel)
+ *   MEL_TILE_64_PERSISTENT   f32: the persistent 64 x 64 kernel of the round step's ragged launches (N % 128 == 0)
+ *   MEL_TILE_64_RING         f32: the specialised-wavefront (loader / MFMA waves) 64 x 64 kernel of the heads' long-K layer
+ *   + MEL_TILE_PLANES_READY  f32_split: W's bf16 planes are still in scratch from an earlier call */
+#define MEL_TILE_AUTO 0
+#define MEL_TILE_64 1
+#define MEL_TILE_128 2
+#define MEL_TILE_WIDE 3
+#define MEL_TILE_64_PERSISTENT 11
+#define MEL_TILE_64_RING 31
+#define MEL_TILE_PLANES_READY 100
+
 /* The dense projection used by every layer above, exposed for tests and tuning:
  *   Y[m, n] = act(sum_k A[m, k] * W[n, k] + bias[n]),  A [M, lda], W [N, K] (nn.Linear layout), Y [M, ldy],
- * all device fp32; K % 32 == 0, N % 64 == 0.  tile: 0 = automatic, 1 = 64x64, 2 = 128x128 workgroup tile, 11 = the
- * persistent 64x64 kernel the ragged launches of the round step use, 31 = the specialised-wavefront (loader / MFMA waves)
- * kernel the heads' long-K first layer uses. */
+ * all device fp32; K % 32 == 0, N % 64 == 0.  tile: MEL_TILE_AUTO, MEL_TILE_64, MEL_TILE_128, MEL_TILE_64_PERSISTENT or
+ * MEL_TILE_64_RING. */
 mel_status mel_gemm_f32(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
                         int64_t M, int32_t N, int32_t K, int32_t relu, int32_t tile, void* stream);
 
@@ -253,11 +269,12 @@ mel_status mel_gemm_f32_splitk(const float* A, int32_t lda, const float* W, cons
                                int64_t parts_floats, void* stream);
 
 /* The same product at MEL_PREC_F32_SPLIT (fp32 operands and results, six exact bf16 partial products per term on the bf16
- * matrix cores): W is split into bf16 planes in `scratch` first.  tile: 0 = the library's choice, 1 = 64 x 64, 2 = 128 x 128
- * (N % 128 == 0), 3 = 128 x 256 with BOTH operands converted to bf16 planes in scratch first (the kernel conv2's projections
- * run on in large forwards, where the conv1 attention stores its rows in that form; N % 256 == 0, N <= 1536, lda == K, ldy % 4 == 0,
- * no split-K; bit-identical to tile 2), + 100 = W's planes are already in scratch (an earlier call with the same W: benchmarks;
- * not with tile 3); ksplit > 1: the 128 x 128 kernel's split-K (K / 16 a multiple of ksplit, >= 4 steps per chunk, ldy % 4 == 0).
+ * matrix cores): W is split into bf16 planes in `scratch` first.  tile: MEL_TILE_AUTO, MEL_TILE_64, MEL_TILE_128
+ * (N % 128 == 0), MEL_TILE_WIDE = 128 x 256 with BOTH operands converted to bf16 planes in scratch first (the kernel conv2's
+ * projections run on in large forwards, where the conv1 attention stores its rows in that form; N % 256 == 0, N <= 1536, lda == K,
+ * ldy % 4 == 0, no split-K; bit-identical to MEL_TILE_128), + MEL_TILE_PLANES_READY = W's planes are already in scratch (an earlier
+ * call with the same W: benchmarks; not with MEL_TILE_WIDE); ksplit > 1: the 128 x 128 kernel's split-K (K / 16 a multiple of
+ * ksplit, >= 4 steps per chunk, ldy % 4 == 0).
  * K % 32 == 0, K >= 128, N % 64 == 0; scratch: device, >= round_up(6 N K, 256) + (ksplit > 1 ? 4 ksplit M N : 0)
  * + (tile 3 ? 6 K M : 0) bytes. */
 mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
@@ -265,8 +282,9 @@ mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const
                               int64_t scratch_bytes, void* stream);
 
 /* The same projection on the bf16 feature path: A [M, lda] and W [N, K] device bf16, bias fp32, fp32
- * accumulation, Y [M, ldy] bf16 (y_f32 = 0) or fp32 (y_f32 = 1); K % 64 == 0, N % 64 == 0, lda % 8 == 0.  tile: 0 = automatic,
- * 2 = 128 x 128, 3 = the 128 x 256 kernel of the large launches (specialised loader / MFMA wavefronts; N % 256 == 0, N <= 1536).
+ * accumulation, Y [M, ldy] bf16 (y_f32 = 0) or fp32 (y_f32 = 1); K % 64 == 0, N % 64 == 0, lda % 8 == 0.  tile: MEL_TILE_AUTO,
+ * MEL_TILE_128, MEL_TILE_WIDE = the 128 x 256 kernel of the large launches (specialised loader / MFMA wavefronts; N % 256 == 0,
+ * N <= 1536).
  * mel_convert_bf16: count (multiple of 8) fp32 values -> bf16, round to nearest even. */
 mel_status mel_gemm_bf16(const void* A, int32_t lda, const void* W, const float* bias, void* Y, int32_t ldy,
                          int64_t M, int32_t N, int32_t K, int32_t relu, int32_t y_f32, int32_t tile, void* stream);

@@ -2,12 +2,11 @@
 // field), fp32-MFMA row GEMMs (gemm_f32.hpp), GATv2 edge-softmax/aggregate, segmented pool, dueling
 // tail, DQN action selection.  Reference semantics: networks/common.py:6-64, l_dgn.py:92-151,
 // hl_dgn.py:82-119 and SURVEY.md Appendix A for the third-party operators.
-#include <cstdlib>
 #include "common.hpp"
-#include "gemm_f32.hpp"
-#include "gemm_bf16.hpp"
-#include "gemm_split.hpp"
-#include "gemm_ring.hpp"
+#include "gemm_launch.hpp"
+#include "plan.hpp"
+#include "attention.hpp"
+#include "heads.hpp"
 
 namespace mel {
 
@@ -21,450 +20,6 @@ void set_error(const char* fmt, ...) {
 
 static thread_local Profiler* g_prof = nullptr;
 Profiler* current_profiler() { return g_prof; }
-
-// ------------------------------------------------------------------------------------------------
-// GEMM dispatch
-// ------------------------------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN>
-static void gemm_launch_t(const GemmArgs* gs, int count, int mode, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    GemmBatch batch{};
-    batch.count = count;
-    int total = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        batch.start[i] = total;
-        const int tiles = ((gs[i].M + BM - 1) / BM) * (gs[i].N / BN);
-        total += (tiles + 7) & ~7;               // keep every problem's ids aligned to the 8 XCDs
-    }
-    batch.start[count] = total;
-    if (mode == GEMM_MODE_ENC)
-        MEL_LAUNCH((gemm_f32_kernel<WM, WN, TM, TN, GEMM_MODE_ENC>), dim3(total), dim3(64 * WM * WN), 0, s, batch);
-    else
-        MEL_LAUNCH((gemm_f32_kernel<WM, WN, TM, TN, GEMM_MODE_PLAIN>), dim3(total), dim3(64 * WM * WN), 0, s, batch);
-}
-
-template <int WM, int WN, int TM, int TN, int TAG = 0>
-static void gemm_launch_persistent(const GemmArgs* gs, int count, int mode, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int LDS_STAGE = (BM + BN) * GEMM_LDS_STRIDE * 4 * 2;
-    constexpr int PER_CU = (160 * 1024) / LDS_STAGE > 4 ? 4 : (160 * 1024) / LDS_STAGE;    // workgroups an LDS-limited CU holds
-    GemmBatch batch{};
-    batch.count = count;
-    long tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        tiles += ((long)((gs[i].M + BM - 1) / BM) * (gs[i].N / BN) + 7) & ~7L;
-    }
-    long grid = 256L * PER_CU;                    // 256 CUs; a multiple of 8 (XCD affinity of tile ids)
-    if (grid > tiles) grid = tiles;
-    if (mode == GEMM_MODE_ENC)
-        MEL_LAUNCH((gemm_f32_persistent_kernel<WM, WN, TM, TN, GEMM_MODE_ENC>), dim3((int)grid), dim3(64 * WM * WN), 0, s, batch);
-    else
-        MEL_LAUNCH((gemm_f32_persistent_kernel<WM, WN, TM, TN, GEMM_MODE_PLAIN, TAG>), dim3((int)grid), dim3(64 * WM * WN), 0, s, batch);
-}
-
-// specialised-wavefront kernel (gemm_ring.hpp): two 8-wave workgroups per CU
-template <int TAG, int BK = GEMM_BK, int WMC = 2>
-static void gemm_launch_ring_t(const GemmArgs* gs, int count, hipStream_t s) {
-    using Cfg = RingCfg<BK, WMC>;
-    GemmBatch batch{};
-    batch.count = count;
-    long tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        tiles += ((long)((gs[i].M + Cfg::BM - 1) / Cfg::BM) * (gs[i].N / 64) * (gs[i].ksplit > 1 ? gs[i].ksplit : 1) + 7) & ~7L;
-    }
-    long grid = 256L * Cfg::WG_PER_CU;
-    if (grid > tiles) grid = tiles;
-    MEL_LAUNCH((gemm_f32_ring_kernel<TAG, BK, WMC>), dim3((int)grid), dim3(Cfg::THREADS), 0, s, batch);
-}
-
-// ragged 64 x 64 launches of the round step, named per call site
-static void gemm_launch_ragged(const GemmArgs* gs, int count, hipStream_t s, int tag) {
-    // Long-K problems (the heads' first layer, K = 1152: 36 K steps per tile) go to the specialised-wavefront kernel:
-    // measured 27.4 vs 30.7 us for the head launches; at K <= 512 the one-role kernel is as fast or faster
-    // (conv2 84 vs 85 us, conv1 46 vs 53 us), see NOTES.md.
-    bool long_k = true;
-    for (int i = 0; i < count; ++i) long_k = long_k && gs[i].K >= 1024 && gs[i].ldy % 4 == 0;
-    if (long_k) {
-        switch (tag) {
-            case 1: gemm_launch_ring_t<1>(gs, count, s); break;
-            case 2: gemm_launch_ring_t<2>(gs, count, s); break;
-            case 3: gemm_launch_ring_t<3>(gs, count, s); break;
-            default: gemm_launch_ring_t<0>(gs, count, s); break;
-        }
-        return;
-    }
-    switch (tag) {
-        case 1: gemm_launch_persistent<2, 2, 1, 1, 1>(gs, count, GEMM_MODE_PLAIN, s); break;
-        case 2: gemm_launch_persistent<2, 2, 1, 1, 2>(gs, count, GEMM_MODE_PLAIN, s); break;
-        case 3: gemm_launch_persistent<2, 2, 1, 1, 3>(gs, count, GEMM_MODE_PLAIN, s); break;
-        default: gemm_launch_persistent<2, 2, 1, 1, 0>(gs, count, GEMM_MODE_PLAIN, s); break;
-    }
-}
-
-// bf16 feature path: one persistent launch for every case (ragged or not)
-template <int WM, int WN, int TM, int TN>
-static void gemm_launch_bf16(const GemmArgs* gs, int count, int mode, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int LDS_WG = (BM + BN) * GEMB_ROW * 16 * 2;
-    constexpr int PER_CU = (160 * 1024) / LDS_WG > 4 ? 4 : (160 * 1024) / LDS_WG;
-    GemmBatch batch{};
-    batch.count = count;
-    long tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        tiles += ((long)((gs[i].M + BM - 1) / BM) * (gs[i].N / BN) * (gs[i].ksplit > 1 ? gs[i].ksplit : 1) + 7) & ~7L;
-    }
-    long grid = 256L * PER_CU;
-    if (grid > tiles) grid = tiles;
-    if (mode == GEMM_MODE_ENC)
-        MEL_LAUNCH((gemm_bf16_kernel<WM, WN, TM, TN, GEMM_MODE_ENC>), dim3((int)grid), dim3(64 * WM * WN), 0, s, batch);
-    else
-        MEL_LAUNCH((gemm_bf16_kernel<WM, WN, TM, TN, GEMM_MODE_PLAIN>), dim3((int)grid), dim3(64 * WM * WN), 0, s, batch);
-}
-
-// split path: a persistent 64 x 64 kernel for small launches, 128 x 128 tiles from MEL_SPLIT_BIG_FROM expected big tiles on
-// (both named per call site like the fp32 one)
-#ifndef MEL_PLANES_FROM
-#define MEL_PLANES_FROM 129          // expected 128 x 256 work items from which conv2 runs on gemm_planes_kernel: up to 256 tiles of
-                                     // 128 x 128 the older kernel has a CU per tile (32 us), beyond it doubles up (42 us at 288); this one
-                                     // takes 33 us for anything up to 256 items
-#endif
-#ifndef MEL_SPLIT_BIG_FROM
-#define MEL_SPLIT_BIG_FROM 192
-#endif
-template <int TAG>
-static void gemm_launch_split_t(const GemmArgs* gs, int count, int mode, hipStream_t s) {
-    GemmBatch batch{};
-    batch.count = count;
-    long tiles = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        tiles += ((long)((gs[i].M + 63) / 64) * (gs[i].N / 64) + 7) & ~7L;
-    }
-    long grid = 256L * 3;                          // 53 KB of LDS per workgroup: three per CU
-    if (grid > tiles) grid = tiles;
-    if (mode == GEMM_MODE_ENC)
-        MEL_LAUNCH((gemm_split_kernel<GEMM_MODE_ENC, TAG>), dim3((int)grid), dim3(256), 0, s, batch);
-    else
-        MEL_LAUNCH((gemm_split_kernel<GEMM_MODE_PLAIN, TAG>), dim3((int)grid), dim3(256), 0, s, batch);
-}
-// 128 x 128 tiles (gemm_split_big_kernel): two workgroups per CU, PLAIN mode, every N a multiple of 128
-template <int TAG>
-static void gemm_launch_split_big_t(const GemmArgs* gs, int count, hipStream_t s) {
-    GemmBatch batch{};
-    batch.count = count;
-    long items = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        items += ((long)((gs[i].M + 127) / 128) * (gs[i].N / 128) * (gs[i].ksplit > 1 ? gs[i].ksplit : 1) + 7) & ~7L;
-    }
-    long grid = 256L * 2;
-    if (grid > items) grid = items;
-    MEL_LAUNCH((gemm_split_big_kernel<TAG>), dim3((int)grid), dim3(256), 0, s, batch);
-}
-static bool split_big_fits(const GemmArgs* gs, int count, int mode) {
-    if (mode != GEMM_MODE_PLAIN) return false;
-    for (int i = 0; i < count; ++i) {
-        const int S = gs[i].ksplit > 1 ? gs[i].ksplit : 1;
-        if (gs[i].N % 128 || gs[i].K % (GEMS2_BK * S) || gs[i].K / GEMS2_BK / S < 4 || gs[i].lda % 4) return false;
-    }
-    return true;
-}
-// big_tiles: expected 128 x 128 tiles of the launch (from the row hints); < 0: the caller forces the 64 x 64 kernel
-static void gemm_launch_split(const GemmArgs* gs, int count, int mode, hipStream_t s, int tag, long big_tiles) {
-    if (big_tiles >= MEL_SPLIT_BIG_FROM && split_big_fits(gs, count, mode)) {
-        switch (tag) {
-            case 2: gemm_launch_split_big_t<2>(gs, count, s); break;
-            case 3: gemm_launch_split_big_t<3>(gs, count, s); break;
-            default: gemm_launch_split_big_t<0>(gs, count, s); break;
-        }
-        return;
-    }
-    switch (tag) {
-        case 1: gemm_launch_split_t<1>(gs, count, mode, s); break;
-        case 2: gemm_launch_split_t<2>(gs, count, mode, s); break;
-        case 3: gemm_launch_split_t<3>(gs, count, mode, s); break;
-        default: gemm_launch_split_t<0>(gs, count, mode, s); break;
-    }
-}
-
-// gemm_planes_kernel (gemm_split.hpp): A as [rows][K / 16][3][16] bf16 planes, W / W_hi as [N / 256][K / 16][256][3][16]
-static bool planes_fit(const GemmArgs* gs, int count) {
-    long ncols = 0;
-    for (int i = 0; i < count; ++i) {
-        const GemmArgs& g = gs[i];
-        if (g.N % GEMP_BN || g.K % GEMS2_BK || g.K / GEMS2_BK < 4 || g.ldy % 4 || g.rscale || g.ksplit > 1) return false;
-        if (g.W_hi && g.split_n % GEMP_BN) return false;
-        if ((size_t)g.M * (size_t)g.K * 6 >= ((size_t)1 << 32)) return false;      // 32-bit operand offsets
-        ncols += g.N;
-    }
-    return count >= 1 && count <= GEMM_MAX_GROUP && ncols <= GEMP_BIAS_FLOATS;
-}
-template <int TAG>
-static void gemm_launch_planes_t(const GemmArgs* gs, int count, hipStream_t s) {
-    GemmBatch batch{};
-    batch.count = count;
-    long items = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        items += ((long)((gs[i].M + 127) / 128) * (gs[i].N / GEMP_BN) + 7) & ~7L;
-    }
-    const long grid = items < 256 ? items : 256;          // one 768-thread workgroup (146 KB of LDS) per CU
-    MEL_LAUNCH((gemm_planes_kernel<TAG>), dim3((int)grid), dim3(768), 0, s, batch);
-}
-static void gemm_launch_planes(const GemmArgs* gs, int count, hipStream_t s, int tag) {
-    switch (tag) {
-        case 2: gemm_launch_planes_t<2>(gs, count, s); break;
-        default: gemm_launch_planes_t<0>(gs, count, s); break;
-    }
-}
-
-// gemm_bf16_wide_kernel (gemm_split.hpp): bf16 rows on both sides, 128 x 256 tiles, 64-k stages
-static bool bf16_wide_fit(const GemmArgs* gs, int count) {
-    long ncols = 0;
-    for (int i = 0; i < count; ++i) {
-        const GemmArgs& g = gs[i];
-        if (!g.bf16 || !g.A || g.N % GEMP_BN || g.K % GEMW_BK || g.K / GEMW_BK < 2 || g.lda % 8 || g.rscale || g.ksplit > 1) return false;
-        if (g.W_hi && g.split_n % GEMP_BN) return false;
-        if ((size_t)g.M * (size_t)g.lda * 2 >= ((size_t)1 << 32) || (size_t)GEMP_BN * g.K * 2 >= ((size_t)1 << 32)) return false;
-        ncols += g.N;
-    }
-    return count >= 1 && count <= GEMM_MAX_GROUP && ncols <= GEMP_BIAS_FLOATS;
-}
-template <int TAG>
-static void gemm_launch_bf16_wide_t(const GemmArgs* gs, int count, hipStream_t s) {
-    GemmBatch batch{};
-    batch.count = count;
-    long items = 0;
-    for (int i = 0; i < count; ++i) {
-        batch.p[i] = gs[i];
-        items += ((long)((gs[i].M + 127) / 128) * (gs[i].N / GEMP_BN) + 7) & ~7L;
-    }
-    const long grid = items < 256 ? items : 256;
-    MEL_LAUNCH((gemm_bf16_wide_kernel<TAG>), dim3((int)grid), dim3(768), 0, s, batch);
-}
-static void gemm_launch_bf16_wide(const GemmArgs* gs, int count, hipStream_t s, int tag) {
-    switch (tag) {
-        case 2: gemm_launch_bf16_wide_t<2>(gs, count, s); break;
-        default: gemm_launch_bf16_wide_t<0>(gs, count, s); break;
-    }
-}
-
-static mel_status check_gemm_shape(const GemmArgs& g, const char* what) {
-    if (g.split && g.K < 128) return fail(MEL_ERR_UNSUPPORTED, "%s: the split path needs K >= 128 (K=%d)", what, g.K);
-    const int bk = g.bf16 ? GEMB_BK : GEMM_BK;
-    if (g.K % bk != 0 || g.N % 64 != 0)
-        return fail(MEL_ERR_UNSUPPORTED, "%s: GEMM needs K %% %d == 0 and N %% 64 == 0 (K=%d N=%d)", what, bk, g.K, g.N);
-    if (g.bf16 && (g.lda % 8 != 0 && g.A))
-        return fail(MEL_ERR_UNSUPPORTED, "%s: bf16 GEMM needs lda %% 8 == 0 (lda=%d)", what, g.lda);
-    return MEL_OK;
-}
-
-mel_status launch_gemm(const GemmArgs& g, int mode, hipStream_t stream, const char* what, long m_hint, int force_tile,
-                       int tag) {
-    if (g.M <= 0) return MEL_OK;
-    if (mel_status st = check_gemm_shape(g, what)) return st;
-    if (m_hint < 0 || m_hint > g.M) m_hint = g.M;
-    if (g.split) {
-        const long big = force_tile == 1 ? -1 : force_tile == 2 ? (1L << 30) : ((m_hint + 127) / 128) * (g.N / 128);
-        if (force_tile == 2 && !split_big_fits(&g, 1, mode)) return fail(MEL_ERR_UNSUPPORTED, "%s: shape does not fit the 128 x 128 split tile", what);
-        gemm_launch_split(&g, 1, mode, stream, tag, big);
-        return check_launch(what);
-    }
-    // encoder (ENC producer): a 64 x 128 tile spans the whole hidden width, so the first layer (VALU work inside the
-    // A-tile producer) is evaluated once per row instead of once per 64-column tile
-    // (fp32: the wide tile wins from about 20 000 rows - HL-DGN's 25 600: 24.8 -> 19.9 us - and loses below - L-DGN's
-    // 16 000: 17 -> 19 us)
-    const bool enc_wide = mode == GEMM_MODE_ENC && force_tile == 0 && g.N % 128 == 0 && (g.bf16 || m_hint >= 20000);
-    if (g.bf16) {
-        if (force_tile == 3) {
-            if (mode != GEMM_MODE_PLAIN || !bf16_wide_fit(&g, 1))
-                return fail(MEL_ERR_UNSUPPORTED, "%s: shape does not fit the 128 x 256 bf16 kernel (N %% 256, K %% 64, lda %% 8)", what);
-            gemm_launch_bf16_wide(&g, 1, stream, tag);
-        } else
-        if (force_tile == 2 && g.N % 128 == 0) gemm_launch_bf16<2, 2, 2, 2>(&g, 1, mode, stream);
-        else if (enc_wide) gemm_launch_bf16<2, 2, 1, 2>(&g, 1, mode, stream);
-        else gemm_launch_bf16<2, 2, 1, 1>(&g, 1, mode, stream);
-        return check_launch(what);
-    }
-    if (enc_wide) {
-        gemm_launch_persistent<2, 2, 1, 2>(&g, 1, mode, stream);
-        return check_launch(what);
-    }
-    if (force_tile == 31 && mode == GEMM_MODE_PLAIN && g.ldy % 4 == 0 && g.K >= 64) {      // specialised-wavefront kernel, 64 x 64
-        gemm_launch_ring_t<0>(&g, 1, stream);
-        return check_launch(what);
-    }
-    if (force_tile == 1 || (force_tile >= 2 && g.N % 128 == 0)) {
-        switch (force_tile) {
-            case 1: gemm_launch_t<2, 2, 1, 1>(&g, 1, mode, stream); break;     //  64 x  64, 4 waves
-            case 2: gemm_launch_t<2, 2, 2, 2>(&g, 1, mode, stream); break;     // 128 x 128, 4 waves
-            case 11: gemm_launch_persistent<2, 2, 1, 1>(&g, 1, mode, stream); break;   // persistent  64 x  64
-            default: return fail(MEL_ERR_INVALID_ARG, "unknown tile %d", force_tile);
-        }
-        return check_launch(what);
-    }
-    // Measured (tools/gemm_bench.py): the 64x64 tile (4x the workgroups, a quarter of the per-wave MFMA
-    // chain, 4 workgroups per CU) wins or ties everywhere except long-K problems with thousands of tiles.
-    const long big = ((m_hint + 127) / 128) * (g.N / 128);
-    if (g.M_dev && mode == GEMM_MODE_PLAIN)
-        gemm_launch_ragged(&g, 1, stream, tag);
-    else if (g.M_dev)
-        gemm_launch_persistent<2, 2, 1, 1>(&g, 1, mode, stream);
-    else if (g.N % 128 == 0 && big >= 1536 && g.K >= 512)
-        gemm_launch_t<2, 2, 2, 2>(&g, 1, mode, stream);
-    else
-        gemm_launch_t<2, 2, 1, 1>(&g, 1, mode, stream);
-    return check_launch(what);
-}
-
-// Skinny long-K problems (the dueling heads' first layer: 4 820 x 256 outputs over K = 1 152 are 304 tiles of 64 x 64 for
-// 512 workgroup slots, one 36-step tile each and half of the slots empty): cut K into S chunks so that the work items
-// fill the chip evenly.  Chunk s writes raw partial products to plane s of `parts`; splitk_finish_kernel sums the planes
-// in order and applies scale / bias / ReLU.  Model of the launch in K steps of one workgroup: (workgroups sharing a
-// CU) x (items per workgroup) x (steps per item + 2 for the hand-over), over the 512 slots of the ring kernel.
-int choose_ksplit(const GemmArgs& g, long m_hint, int max_split) {
-    if (g.K < 512 || g.ldy % 4 || g.N % 64 || g.K % GEMB_BK) return 1;
-    if (g.split) {
-        // 128 x 128 split kernel: 512 slots (two workgroups per CU); steps of 16 k, ~4 steps of hand-over per work item
-        if (g.N % 128 || g.lda % 4) return 1;
-        const long tiles = ((m_hint + 127) / 128) * (g.N / 128);
-        const int KT = g.K / GEMS2_BK;
-        int best = 1;
-        long best_cost = 0;
-        for (int S = 1; S <= max_split; ++S) {
-            if (KT % S || KT / S < 4) continue;
-            const long items = tiles * S, slots = items < 512 ? items : 512;
-            const long cost = ((slots + 255) / 256) * ((items + slots - 1) / slots) * (KT / S + 4);
-            if (S == 1 || cost < best_cost) best = S, best_cost = cost;
-        }
-        return best * tiles >= MEL_SPLIT_BIG_FROM ? best : 1;
-    }
-    const long tiles = ((m_hint + 63) / 64) * (g.N / 64);
-    if (g.bf16) {
-        // bf16 one-role kernel: 1 024 slots, latency bound at these sizes - items per slot x (steps per item + 2)
-        const int KT = g.K / GEMB_BK;
-        int best = 1;
-        long best_cost = 0;
-        for (int S = 1; S <= max_split; ++S) {
-            if (KT % S || KT / S < 2) continue;
-            const long items = tiles * S, slots = items < 1024 ? items : 1024;
-            const long cost = ((items + slots - 1) / slots) * (KT / S + 2);
-            if (S == 1 || cost < best_cost) best = S, best_cost = cost;
-        }
-        return best;
-    }
-    const int KT = g.K / GEMM_BK;
-    int best = 1;
-    long best_cost = 0;
-    for (int S = 1; S <= max_split; ++S) {
-        if (KT % S || KT / S < 2) continue;        // (the hand-over buffer needs two steps between tiles)
-        const long items = tiles * S, slots = items < 512 ? items : 512;
-        const long cost = ((slots + 255) / 256) * ((items + slots - 1) / slots) * (KT / S + 2);
-        if (S == 1 || cost < best_cost) best = S, best_cost = cost;
-    }
-    return best;
-}
-
-mel_status launch_gemm_splitk(const GemmArgs& g, int S, float* parts, long part_stride, hipStream_t stream,
-                              const char* what, long m_hint, int tag, bool finish = true) {
-    if (g.M <= 0) return MEL_OK;
-    if (mel_status st = check_gemm_shape(g, what)) return st;
-    if (S < 2 || (g.K / (g.bf16 ? GEMB_BK : g.split ? GEMS2_BK : GEMM_BK)) % S || !parts || part_stride < (long)g.M * g.N)
-        return fail(MEL_ERR_INVALID_ARG, "%s: bad split-K request (S=%d)", what, S);
-    GemmArgs p = g;
-    p.Y = parts, p.ldy = g.N, p.ksplit = S, p.part_stride = part_stride;
-    if (g.split) {
-        if (!split_big_fits(&p, 1, GEMM_MODE_PLAIN)) return fail(MEL_ERR_UNSUPPORTED, "%s: shape does not fit the 128 x 128 split tile", what);
-        gemm_launch_split(&p, 1, GEMM_MODE_PLAIN, stream, tag, 1L << 30);
-    } else if (g.bf16) {
-        p.y_f32 = 1;
-        gemm_launch_bf16<2, 2, 1, 1>(&p, 1, GEMM_MODE_PLAIN, stream);
-    } else {
-        switch (tag) {
-            case 3: gemm_launch_ring_t<3>(&p, 1, stream); break;
-            default: gemm_launch_ring_t<0>(&p, 1, stream); break;
-        }
-    }
-    if (mel_status st = check_launch(what)) return st;
-    if (!finish) return MEL_OK;               // the caller's next launch sums the planes itself
-    SplitKFinish f{parts, part_stride, S, g.N, g.M, g.M_dev, g.bias, g.bias_hi, g.split_n, g.rscale, g.relu, g.Y, g.ldy};
-    if (m_hint < 0 || m_hint > g.M) m_hint = g.M;
-    long blocks = (m_hint * (g.N / 4) + 255) / 256;
-    blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
-    MEL_LAUNCH(splitk_finish_kernel, dim3((int)blocks), dim3(256), 0, stream, f);
-    return check_launch(what);
-}
-
-mel_status launch_gemm_group(const GemmArgs* gs, const long* hints, int count, hipStream_t stream, const char* what,
-                             int tag) {
-    if (count < 1 || count > GEMM_MAX_GROUP) return fail(MEL_ERR_INVALID_ARG, "%s: group of %d", what, count);
-    long big = 0;
-    bool n128 = true, long_k = true;
-    for (int i = 0; i < count; ++i) {
-        if (gs[i].M <= 0) return fail(MEL_ERR_INVALID_ARG, "%s: empty problem in group", what);
-        if (mel_status st = check_gemm_shape(gs[i], what)) return st;
-        const long h = (hints && hints[i] >= 0 && hints[i] <= gs[i].M) ? hints[i] : gs[i].M;
-        big += ((h + 127) / 128) * (gs[i].N / 128);
-        n128 = n128 && gs[i].N % 128 == 0;
-        long_k = long_k && gs[i].K >= 512;
-    }
-    if (!gs[0].split && !gs[0].bf16 && big >= MEL_SPLIT_BIG_FROM) {
-        // MEL_PREC_F32_AUTO: every problem carries the bf16 planes of its weights and the launch is large enough for the
-        // 128 x 128 split kernel to win (conv2 in the L-DGN step: 52 against 83 us) - same fp32-accurate results
-        GemmArgs t[GEMM_MAX_GROUP];
-        bool alt = true;
-        for (int i = 0; i < count; ++i) {
-            t[i] = gs[i];
-            alt = alt && gs[i].Ws && !gs[i].split && !gs[i].bf16 && (!gs[i].W_hi || gs[i].Ws_hi);
-            t[i].W = gs[i].Ws, t[i].W_hi = gs[i].W_hi ? gs[i].Ws_hi : nullptr, t[i].split = 1;
-        }
-        if (alt && split_big_fits(t, count, GEMM_MODE_PLAIN)) {
-            gemm_launch_split(t, count, GEMM_MODE_PLAIN, stream, tag, big);
-            return check_launch(what);
-        }
-    }
-    if (gs[0].split) {
-        for (int i = 1; i < count; ++i)
-            if (!gs[i].split) return fail(MEL_ERR_INVALID_ARG, "%s: mixed precisions in one group", what);
-        gemm_launch_split(gs, count, GEMM_MODE_PLAIN, stream, tag, big);
-        return check_launch(what);
-    }
-    if (gs[0].bf16) {
-        for (int i = 1; i < count; ++i)
-            if (!gs[i].bf16) return fail(MEL_ERR_INVALID_ARG, "%s: mixed precisions in one group", what);
-        // large launches: 128 x 256 tiles (conv2 of the bf16 feature path: 97 MB of operands through the L2 instead of 0.5 GB)
-        static const bool wide_off = getenv("MEL_NO_BF16_WIDE") != nullptr;
-        long items = 0;
-        for (int i = 0; i < count; ++i) {
-            const long h = (hints && hints[i] >= 0 && hints[i] <= gs[i].M) ? hints[i] : gs[i].M;
-            items += ((h + 127) / 128) * (gs[i].N / GEMP_BN);
-        }
-        if (!wide_off && items >= MEL_PLANES_FROM && bf16_wide_fit(gs, count)) gemm_launch_bf16_wide(gs, count, stream, tag);
-        else gemm_launch_bf16<2, 2, 1, 1>(gs, count, GEMM_MODE_PLAIN, stream);
-        return check_launch(what);
-    }
-    bool ragged = false;
-    for (int i = 0; i < count; ++i) ragged = ragged || gs[i].M_dev != nullptr;
-    if (ragged)       // device-side row counts: a fixed grid walks the tiles instead of a worst-case grid exiting
-        gemm_launch_ragged(gs, count, stream, tag);
-    else if (n128 && long_k && big >= 1536)
-        gemm_launch_t<2, 2, 2, 2>(gs, count, GEMM_MODE_PLAIN, stream);
-    else
-        gemm_launch_t<2, 2, 1, 1>(gs, count, GEMM_MODE_PLAIN, stream);
-    return check_launch(what);
-}
-
-}  // namespace mel
-
-#include "plan.hpp"
-#include "attention.hpp"
-#include "heads.hpp"
-
-namespace mel {
 
 // The row lists of a forward and the encoder rows of its node-feature table in ONE launch: the first `gemm_blocks`
 // workgroups are 64 x 64 tiles of the (feature-domain) encoder GEMM, the rest run plan_lists.  The two are independent (the
@@ -807,32 +362,23 @@ static mel_status run_heads(const mel_weights* w, const ProjWeights& pw, const F
         const mel_linear& v = w->v_head.layer[0];
         const mel_linear& q1 = w->q_head.layer[1];
         const mel_linear& v1 = w->v_head.layer[1];
-        GemmArgs g;
-        g.A = in_q, g.lda = ld_q, g.W = pw.q[0], g.W_hi = pw.v[0], g.split_n = q.out_dim;
-        g.Y = L.hpart, g.ldy = 2 * HF_W, g.M = (int)rows, g.M_dev = rows_dev, g.N = 2 * HF_W, g.K = q.in_dim;
-        g.bf16 = bf, g.split = sp, g.y_f32 = 1;
-        const long hint = rows_hint < 0 || rows_hint > rows ? rows : rows_hint;
-        int S = choose_ksplit(g, hint, HEAD_KSPLIT_MAX);
-        if (pw.alt && pw.alt->q[0] && pw.alt->v[0]) {     // MEL_PREC_F32_AUTO: the split kernel when its work items fill the chip
-            GemmArgs t = g;
-            t.W = pw.alt->q[0], t.W_hi = pw.alt->v[0], t.split = 1;
-            const int St = choose_ksplit(t, hint, HEAD_KSPLIT_MAX);
-            const long tiles = ((hint + 127) / 128) * (t.N / 128);
-            t.ksplit = St > 1 ? St : 0;
-            if ((St > 1 || tiles >= MEL_SPLIT_BIG_FROM) && split_big_fits(&t, 1, GEMM_MODE_PLAIN)) {
-                t.ksplit = 0;
-                g = t, S = St;
-            }
-        }
         if (q.in_dim == v.in_dim && q.out_dim == HF_W && v.out_dim == HF_W && q1.in_dim == HF_W &&
             q1.out_dim == HF_W && v1.in_dim == HF_W && v1.out_dim == HF_W && w->q_head.layer[2].out_dim <= HF_MAX_ACTIONS &&
             w->v_head.layer[2].out_dim == 1 && q1.weight && v1.weight) {
             const long ps = (long)L.rows_cap * 2 * HF_W;
+            GemmArgs g;
+            g.A = in_q, g.lda = ld_q, g.W = pw.q[0], g.W_hi = pw.v[0], g.split_n = q.out_dim;
+            g.Y = L.hpart, g.ldy = 2 * HF_W, g.M = (int)rows, g.M_dev = rows_dev, g.N = 2 * HF_W, g.K = q.in_dim;
+            g.bf16 = bf, g.split = sp, g.y_f32 = 1;
+            if (pw.alt) g.Ws = pw.alt->q[0], g.Ws_hi = pw.alt->v[0];
+            const long hint = rows_hint < 0 || rows_hint > rows ? rows : rows_hint;
+            GemmRequest rq;     // split-K into L.hpart where the chunks fill the chip; head_finish_kernel sums the planes
+            rq.max_ksplit = HEAD_KSPLIT_MAX, rq.parts = L.hpart, rq.part_stride = ps;
+            const GemmPlan plan = plan_gemm(&g, &hint, 1, rq);
+            const int S = plan.ksplit;
             {
                 StageScope t(MEL_STAGE_HEAD_HIDDEN, s);
-                if (S > 1) {
-                    if (mel_status st = launch_gemm_splitk(g, S, L.hpart, ps, s, "head hidden (Q|V), split-K", hint, 3, false)) return st;
-                } else if (mel_status st = launch_gemm(g, GEMM_MODE_PLAIN, s, "head hidden (Q|V), raw", hint, 0, 3)) return st;
+                if (mel_status st = launch_plan(plan, s, 3, S > 1 ? "head hidden (Q|V), split-K" : "head hidden (Q|V), raw")) return st;
             }
             StageScope t(MEL_STAGE_HEAD_TAIL, s);
             HeadFinish f{L.hpart, ps, S, (int)rows, rows_dev, q.bias, v.bias, q1, v1, w->q_head.layer[2], w->v_head.layer[2],
@@ -864,11 +410,13 @@ static mel_status run_heads(const mel_weights* w, const ProjWeights& pw, const F
             g.Y = out, g.ldy = ldo, g.M = (int)rows, g.M_dev = rows_dev, g.N = ldo, g.K = q.in_dim, g.relu = 1;
             g.bf16 = bf, g.split = sp, g.y_f32 = (i + 2 == nl);       // the tail reads fp32
             // (the plane sum writes fp32: on the bf16 path only where the consumer reads fp32)
-            const int S = (bf && !g.y_f32) ? 1 : choose_ksplit(g, rows_hint < 0 || rows_hint > rows ? rows : rows_hint, HEAD_KSPLIT_MAX);
-            if (S > 1) {
-                if (mel_status st = launch_gemm_splitk(g, S, L.hpart, (long)L.rows_cap * ldo, s, "head hidden (Q|V), split-K",
-                                                       rows_hint, 3)) return st;
-            } else if (mel_status st = launch_gemm(g, GEMM_MODE_PLAIN, s, "head hidden (Q|V)", rows_hint, 0, 3)) return st;
+            GemmRequest rq;
+            rq.max_ksplit = (bf && !g.y_f32) ? 1 : HEAD_KSPLIT_MAX, rq.parts = L.hpart, rq.part_stride = (long)L.rows_cap * ldo;
+            const GemmPlan plan = plan_gemm(&g, &rows_hint, 1, rq);
+            const char* what = plan.ksplit > 1 ? "head hidden (Q|V), split-K" : "head hidden (Q|V)";
+            if (mel_status st = launch_plan(plan, s, 3, what)) return st;
+            if (plan.ksplit > 1)
+                if (mel_status st = launch_splitk_finish(g, plan, rows_hint, s, what)) return st;
         } else {
             GemmArgs g[2];
             // element offset of the V half inside a row: in elements of the buffer's type (bf16 halves the bytes)
@@ -990,27 +538,29 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
     const bool table = (w->flags & MEL_FWD_INTEGER_FEATURES) && w->in_dim == 5 && hint1 + hint2 >= 2L * T;
     bool fused_enc = false;
-    // conv2's projections on gemm_planes_kernel (both operands as bf16 planes in blocks, gemm_split.hpp): decided HERE, because
-    // the conv1 attention then stores h1 already split, as that kernel's A operand.  Large launches of the fp32-accurate
-    // paths only: a launch of fewer work items than CUs stays on the 128 x 128 / 64 x 64 kernels.
-    const ProjWeights* planes = sp ? &pw : pw.alt;
+    // conv2's projections, planned HERE: on gemm_planes_kernel (both operands as bf16 planes in blocks, gemm_split.hpp) the
+    // conv1 attention stores h1 already split, as that kernel's A operand.  (h1 rows are masked by the decision-maker flag,
+    // l_dgn.py:128: the conv1 attention applies it as it stores them.)
     GemmArgs c2[2];
-    {
-        c2[0].A = L.h1, c2[0].lda = hc, c2[0].bias = w->conv2.lin_l.bias, c2[0].split = 1;
-        c2[0].Y = L.xl2, c2[0].ldy = srcw, c2[0].M = U1, c2[0].M_dev = n1, c2[0].N = srcw, c2[0].K = hc;
-        if (tconv) c2[0].bias_hi = w->conv2.lin_v.bias, c2[0].split_n = hc;
-        c2[1].A = L.h1, c2[1].lda = hc, c2[1].arow = L.plan.arow_g, c2[1].bias = w->conv2.lin_r.bias, c2[1].split = 1;
-        c2[1].Y = L.xr2, c2[1].ldy = hc, c2[1].M = R, c2[1].M_dev = nL, c2[1].N = hc, c2[1].K = hc;
-        if (planes) {
-            c2[0].W = planes->c2l_blk, c2[1].W = planes->c2r_blk;
-            if (tconv) c2[0].W_hi = planes->c2v_blk;
-        }
+    c2[0].bf16 = c2[1].bf16 = bf, c2[0].split = c2[1].split = sp;
+    c2[0].A = L.h1, c2[0].lda = hc;
+    c2[0].W = pw.c2l, c2[0].bias = w->conv2.lin_l.bias;
+    c2[0].Y = L.xl2, c2[0].ldy = srcw, c2[0].M = U1, c2[0].M_dev = n1, c2[0].N = srcw, c2[0].K = hc;
+    if (tconv) c2[0].W_hi = pw.c2v, c2[0].bias_hi = w->conv2.lin_v.bias, c2[0].split_n = hc;
+    c2[1].A = L.h1, c2[1].lda = hc, c2[1].arow = L.plan.arow_g;
+    c2[1].W = pw.c2r, c2[1].bias = w->conv2.lin_r.bias;
+    if (pw.alt) c2[0].Ws = pw.alt->c2l, c2[0].Ws_hi = tconv ? pw.alt->c2v : nullptr, c2[1].Ws = pw.alt->c2r;
+    c2[1].Y = L.xr2, c2[1].ldy = hc, c2[1].M = R, c2[1].M_dev = nL, c2[1].N = hc, c2[1].K = hc;
+    const long c2_hints[2] = {hint1, hintL};
+    const ProjWeights* planes = sp ? &pw : pw.alt;
+    GemmRequest c2_rq;
+    c2_rq.group = true;
+    PlaneBlocks c2_blocks[2];
+    if (planes && hc % 4 == 0 && hc / 64 >= 4) {      // (the forms of h1 the conv1 attention can store as planes)
+        c2_blocks[0] = {planes->c2l_blk, tconv ? planes->c2v_blk : nullptr}, c2_blocks[1] = {planes->c2r_blk, nullptr};
+        c2_rq.blocks = c2_blocks;
     }
-    const long c2_items = ((hint1 + 127) / 128) * (srcw / GEMP_BN) + ((hintL + 127) / 128) * (hc / GEMP_BN);
-    static const bool planes_off = getenv("MEL_NO_PLANES_GEMM") != nullptr;         // A/B switch for bench and tests
-    static const long planes_from = getenv("MEL_PLANES_FROM") ? atol(getenv("MEL_PLANES_FROM")) : MEL_PLANES_FROM;      // (tuning)
-    const bool conv2_planes = !planes_off && !bf && planes && c2[0].W && c2[1].W && (!tconv || c2[0].W_hi) && hc % 4 == 0 &&
-                              hc / 64 >= 4 && c2_items >= planes_from && planes_fit(c2, 2);
+    const GemmPlan conv2 = plan_gemm(c2, c2_hints, 2, c2_rq);
 
     {
         StageScope t(MEL_STAGE_PLAN, s);
@@ -1037,13 +587,13 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
             g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
             g.W = bf ? w->encoder.layer[1].weight : pw.enc1, g.bias = w->encoder.layer[1].bias, g.y_bf16 = bf;
             g.Y = L.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-            if (mel_status st = check_gemm_shape(g, "encoder (feature tuples)")) return st;
-            GemmBatch batch{};
-            batch.count = 1, batch.p[0] = g, batch.start[0] = 0;
-            const int tiles = ((((T + 63) / 64) * (hidden / 64)) + 7) & ~7;
-            batch.start[1] = tiles;
-            if (n > 64) MEL_LAUNCH(plan_enc_kernel<2>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, batch, tiles);
-            else MEL_LAUNCH(plan_enc_kernel<1>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, batch, tiles);
+            GemmRequest rq;                         // the 64 x 64 tiles of gemm_f32_kernel, one workgroup each
+            rq.mode = GEMM_MODE_ENC, rq.force_tile = MEL_TILE_64;
+            const GemmPlan enc = plan_gemm(&g, nullptr, 1, rq);
+            if (enc.status) return fail(enc.status, "encoder (feature tuples): %s", enc.why);
+            const int tiles = enc.grid;
+            if (n > 64) MEL_LAUNCH(plan_enc_kernel<2>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
+            else MEL_LAUNCH(plan_enc_kernel<1>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
         } else if (n > 64) {
             MEL_LAUNCH(plan_lists_kernel<2>, dim3((bs + 3) / 4), dim3(256), 0, s, pa);
         } else {
@@ -1091,30 +641,15 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.desc = L.plan.desc1, a.rows_dev = n1, a.rows_cap = U1, a.rows_hint = hint1;
         a.lanes_per_head = w->conv1.channels / (hc / 64);
         a.out = L.h1, a.ldo = hc, a.xcat = L.xcat, a.ld_cat = latent, a.hidden = hidden, a.h0 = ft.h0;
-        if (conv2_planes) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
+        if (conv2.kernel == GemmKernel::PLANES) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
         a.out_scale = L.plan.dm1;       // the decision-maker mask (l_dgn.py:128) is applied as h1 is stored; x_2 is taken before it
         a.fid = table ? L.plan.fid : nullptr;
         StageScope t(MEL_STAGE_CONV1_ATT, s);
         if (mel_status st = launch_attend<ATT_ROWS>(a, hc, s, "conv1 attention")) return st;
     }
-    {   // conv2.lin_l on the U1 rows + conv2.lin_r on the agent rows, one grouped launch (h1 rows are already masked by the
-        // decision-maker flag, l_dgn.py:128: the conv1 attention applied it as it stored them)
-        GemmArgs g[2];
-        g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = sp;
-        g[0].A = L.h1, g[0].lda = hc;
-        g[0].W = pw.c2l, g[0].bias = w->conv2.lin_l.bias;
-        g[0].Y = L.xl2, g[0].ldy = srcw, g[0].M = U1, g[0].M_dev = n1, g[0].N = srcw, g[0].K = hc;
-        if (tconv) g[0].W_hi = pw.c2v, g[0].bias_hi = w->conv2.lin_v.bias, g[0].split_n = hc;
-        g[1].A = L.h1, g[1].lda = hc, g[1].arow = L.plan.arow_g;
-        g[1].W = pw.c2r, g[1].bias = w->conv2.lin_r.bias;
-        if (pw.alt) g[0].Ws = pw.alt->c2l, g[0].Ws_hi = tconv ? pw.alt->c2v : nullptr, g[1].Ws = pw.alt->c2r;
-        g[1].Y = L.xr2, g[1].ldy = hc, g[1].M = R, g[1].M_dev = nL, g[1].N = hc, g[1].K = hc;
-        const long hints[2] = {hint1, hintL};
+    {   // conv2.lin_l on the U1 rows + conv2.lin_r on the agent rows, one grouped launch
         StageScope t(MEL_STAGE_CONV2_LIN, s);
-        if (conv2_planes) {
-            gemm_launch_planes(c2, 2, s, 2);
-            if (mel_status st = check_launch("conv2.lin_l + lin_r (planes)")) return st;
-        } else if (mel_status st = launch_gemm_group(g, hints, 2, s, "conv2.lin_l + lin_r", 2)) return st;
+        if (mel_status st = launch_plan(conv2, s, 2, "conv2.lin_l + lin_r")) return st;
     }
     {   // conv2 attention, one target per agent row -> x_3
         AttArgs a{};
@@ -1329,13 +864,13 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
             g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
             g.W = bf ? w->encoder.layer[1].weight : pw.enc1, g.bias = w->encoder.layer[1].bias, g.y_bf16 = bf;
             g.Y = L.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-            if (mel_status st = check_gemm_shape(g, "encoder (feature tuples)")) return st;
-            GemmBatch batch{};
-            batch.count = 1, batch.p[0] = g, batch.start[0] = 0;
-            const int tiles = ((((T + 63) / 64) * (hidden / 64)) + 7) & ~7;
-            batch.start[1] = tiles;
+            GemmRequest rq;                         // the 64 x 64 tiles of gemm_f32_kernel, one workgroup each
+            rq.mode = GEMM_MODE_ENC, rq.force_tile = MEL_TILE_64;
+            const GemmPlan enc = plan_gemm(&g, nullptr, 1, rq);
+            if (enc.status) return fail(enc.status, "encoder (feature tuples): %s", enc.why);
+            const int tiles = enc.grid;
             MEL_LAUNCH(fid_enc_kernel, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols, L.plan, T,
-                       batch, tiles);
+                       enc.batch, tiles);
         } else {
             MEL_LAUNCH(feature_ids_kernel, dim3((bs + 3) / 4), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols, L.plan,
                        table ? T : 0);
@@ -1451,7 +986,7 @@ mel_status mel_gemm_f32_splitk(const float* A, int32_t lda, const float* W, cons
     clear_stale_error();
     GemmArgs g;
     g.A = A, g.lda = lda, g.W = W, g.bias = bias, g.Y = Y, g.ldy = ldy, g.M = (int)M, g.N = N, g.K = K, g.relu = relu;
-    return launch_gemm_splitk(g, ksplit, parts, (long)M * N, static_cast<hipStream_t>(stream), "mel_gemm_f32_splitk", -1, 0);
+    return launch_gemm_splitk(g, ksplit, parts, (long)M * N, static_cast<hipStream_t>(stream), "mel_gemm_f32_splitk");
 }
 
 mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
@@ -1460,7 +995,7 @@ mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const
     if (!A || !W || !Y || !scratch || M <= 0 || M > (1ll << 30) || lda < K || ldy < N || N < 64 || K < 128)
         return fail(MEL_ERR_INVALID_ARG, "bad split-precision gemm arguments");
     const int64_t plane_bytes = ((int64_t)6 * N * K + 255) & ~255ll;
-    const bool blocks = tile % 100 == 3;                // gemm_planes_kernel: A goes through bf16 planes in scratch as well
+    const bool blocks = tile % MEL_TILE_PLANES_READY == MEL_TILE_WIDE;    // gemm_planes_kernel: A goes through bf16 planes in scratch as well
     const int64_t a_bytes = blocks ? M * K * 6 : 0;
     const int64_t need = plane_bytes + a_bytes + (ksplit > 1 ? (int64_t)ksplit * M * N * 4 : 0);
     if (K % 32 || N % 64 || scratch_bytes < need)
@@ -1471,7 +1006,10 @@ mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const
         GemmArgs g;
         g.A = reinterpret_cast<const float*>(static_cast<char*>(scratch) + plane_bytes), g.lda = K;
         g.W = static_cast<const float*>(scratch), g.bias = bias, g.Y = Y, g.ldy = ldy, g.M = (int)M, g.N = N, g.K = K, g.relu = relu, g.split = 1;
-        if (ksplit > 1 || lda != K || M * K >= (1ll << 31) || !planes_fit(&g, 1))
+        GemmRequest rq;
+        rq.force_tile = MEL_TILE_WIDE;
+        const GemmPlan plan = plan_gemm(&g, nullptr, 1, rq);
+        if (ksplit > 1 || lda != K || M * K >= (1ll << 31) || plan.status)
             return fail(MEL_ERR_UNSUPPORTED, "split-precision gemm, 128 x 256 planes kernel: N %% 256 == 0, N <= %d, K / 16 >= 4, lda == K, "
                                              "ldy %% 4 == 0, no split-K", GEMP_BIAS_FLOATS);
         SplitBatch b{};
@@ -1483,24 +1021,23 @@ mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const
         b.start[2] = b.start[1] + (int)((M * K / 4 + 255) / 256);
         MEL_LAUNCH(split_weights_kernel, dim3(b.start[2]), dim3(256), 0, s, b);
         if (mel_status st = check_launch("operands -> bf16 planes")) return st;
-        gemm_launch_planes(&g, 1, s, 0);
-        return check_launch("mel_gemm_f32_split (planes)");
+        return launch_plan(plan, s, 0, "mel_gemm_f32_split (planes)");
     }
     SplitBatch b{};
     b.n = 1, b.src[0] = W, b.dst[0] = static_cast<uint16_t*>(scratch), b.count[0] = N * K, b.K[0] = K, b.start[0] = 0;
     b.start[1] = (int)(((int64_t)N * K / 4 + 255) / 256);
-    if (tile < 100) {                                   // tile + 100: the planes of an earlier call are still in scratch
+    if (tile < MEL_TILE_PLANES_READY) {
         MEL_LAUNCH(split_weights_kernel, dim3(b.start[1]), dim3(256), 0, s, b);
         if (mel_status st = check_launch("weights -> bf16 planes")) return st;
     } else {
-        tile -= 100;
+        tile -= MEL_TILE_PLANES_READY;
     }
     GemmArgs g;
     g.A = A, g.lda = lda, g.W = static_cast<const float*>(scratch), g.bias = bias, g.Y = Y, g.ldy = ldy, g.M = (int)M, g.N = N, g.K = K;
     g.relu = relu, g.split = 1;
     if (ksplit > 1)
         return launch_gemm_splitk(g, ksplit, reinterpret_cast<float*>(static_cast<char*>(scratch) + plane_bytes), (long)M * N, s,
-                                  "mel_gemm_f32_split", -1, 0);
+                                  "mel_gemm_f32_split");
     return launch_gemm(g, GEMM_MODE_PLAIN, s, "mel_gemm_f32_split", -1, tile);
 }
 

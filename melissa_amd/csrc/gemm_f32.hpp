@@ -692,12 +692,4 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_f32_persistent_kernel(Ge
 #endif
 }
 
-// Host-side dispatch: picks the tile so that the launch keeps the 256 CUs busy.  `m_hint` is the row
-// count the caller expects (ragged lists are sized on the device; the grid still covers g.M rows).
-mel_status launch_gemm(const GemmArgs& g, int mode, hipStream_t stream, const char* what, long m_hint = -1,
-                       int force_tile = 0, int tag = 0);
-// Several PLAIN problems in one launch; hints[i] = expected rows of problem i (-1 = g.M).
-mel_status launch_gemm_group(const GemmArgs* gs, const long* hints, int count, hipStream_t stream, const char* what,
-                             int tag = 0);
-
 }  // namespace mel
