@@ -655,6 +655,52 @@ mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int
                              const float* discount, uint64_t seed, uint64_t* draw_counter, int32_t* scratch,
                              const mel_replay_batch* out, void* stream);
 
+/* Prioritized experience replay over a mel_round_replay: the counterpart of [3P] tianshou 1.0.0 PrioritizedVectorReplayBuffer, which
+ * every training script of the reference switches to with --prio-buffer --alpha 0.6 --beta 0.4 (common.py:52,64-65,
+ * l_dgn.py:169-176).  Parity unpinned: tianshou is restated from its published behaviour.  A transition is (env, slot, agent) with
+ * agent in the record's acted set; buffer order is the memory order of prio.  All pointers are caller-owned DEVICE memory:
+ *   prio      float  [B, K, N]  p^alpha of every transition; 0 for agents that did not act and slots not yet filled (start: 0)
+ *   rec_sum   double [B * K]    scratch: per-record sums
+ *   prefix    double [B * K + 1] scratch: their exclusive prefix sums, prefix[B * K] = total
+ *   seen      int32  [B]        cursor[b] at the last sample (start: 0): records written since then are initialised lazily to
+ *                               max_prio^alpha by the next sample - upstream's add(), without touching mel_env_round
+ *   max_prio / min_prio float scalars: largest / smallest raw p = |td| + eps written back so far (start: 1.0)
+ * alpha, beta >= 0; weight_norm != 0 divides the importance weights by their maximum over the batch (upstream's default). */
+typedef struct mel_replay_priority {
+    float*   prio;
+    double*  rec_sum;
+    double*  prefix;
+    int32_t* seen;
+    float*   max_prio;
+    float*   min_prio;
+    double   alpha;
+    double   beta;
+    int32_t  weight_norm;
+    int32_t  reserved;
+} mel_replay_priority;
+
+/* mel_replay_sample with draws proportional to priority (PrioritizedReplayBuffer.sample_indices + get_weight, then
+ * compute_nstep_return): scalar = u * sum(prio), u = (splitmix64(seed, *draw_counter, sample index) >> 11) * 2^-53; the sample is
+ * the first transition, in buffer order, whose inclusive prefix sum exceeds it (float64 sums).  Outputs: everything
+ * mel_replay_sample writes, plus weight float [batch] (device) = (prio / min_prio)^-beta in float64 [/ max over the batch].  Two
+ * launches (refresh grid-wide, then one workgroup); also sets seen[b] = cursor[b] and increments *draw_counter.  An empty replay
+ * samples like mel_replay_sample (index 0, weight 1).
+ * MEL_ERR_INVALID_ARG: a null argument or incomplete struct, alpha < 0, beta < 0, batch outside [1, 1024], n_step outside
+ * [1, MEL_REPLAY_MAX_NSTEP], n_envs * capacity > 2^24, nb_sibling without active_nb. */
+mel_status mel_replay_sample_prio(const mel_round_replay* replay, const mel_replay_priority* priority, int64_t n_envs, int32_t n_nodes,
+                                  int32_t batch, int32_t n_step, const float* discount, uint64_t seed, uint64_t* draw_counter,
+                                  const mel_replay_batch* out, float* weight, void* stream);
+
+/* PrioritizedReplayBuffer.update_weight(indices, td), called by [3P] BasePolicy.post_process_fn after every update with the TD
+ * error the loss left in batch.weight: p = |td| + eps in float (eps = FLT_EPSILON), prio[env, slot, agent] = powf(p, alpha) - among
+ * samples that name the same transition the highest sample index wins, as numpy's assignment does -, max_prio = max(max_prio,
+ * max p), min_prio = min(min_prio, min p).  env / slot / agent: device int64 [batch] (a sampled batch's), td: device float [batch].
+ * One workgroup, no atomics.  Samples outside [0, B) x [0, capacity) x [0, N) are skipped.
+ * MEL_ERR_INVALID_ARG: null / incomplete struct, alpha < 0, beta < 0, index arrays or td missing, batch outside [1, 1024]. */
+mel_status mel_replay_update_priority(const mel_replay_priority* priority, int64_t n_envs, int32_t capacity, int32_t n_nodes,
+                                      int32_t batch, const int64_t* env, const int64_t* slot, const int64_t* agent, const float* td,
+                                      void* stream);
+
 /* One Adam update of up to MEL_ADAM_MAX_TENSORS parameter tensors in one launch ([3P] torch.optim.Adam as the reference
  * configures it, l_dgn.py:207: no amsgrad, L2 weight decay): exp_avg <- lerp(exp_avg, g, 1 - beta1); exp_avg_sq <- beta2 exp_avg_sq
  * + (1 - beta2) g^2; param <- param - lr / (1 - beta1^t) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps).  All pointers
@@ -727,7 +773,8 @@ int32_t    mel_prof_read(void* prof, double* ms_sum, int64_t* count);
 const char* mel_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, for binding authors to check their mirrors
  * against: which = 0 mel_linear, 1 mel_gatv2, 2 mel_mlp, 3 mel_weights, 4 mel_select, 5 mel_env_batch,
- * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors;
+ * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors,
+ * 13 mel_replay_priority;
  * 0 for anything else. */
 size_t mel_abi_sizeof(int32_t which);
 const char* mel_version(void);

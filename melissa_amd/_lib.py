@@ -36,7 +36,7 @@ SET_HAS_MESSAGE, SET_ORIGIN, SET_INTERESTED, SET_SCRIPTED, SET_TRUNCATED, SET_AL
 
 # every symbol include/melissa_hip.h declares
 EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_tables", "mel_prepared_weights_bytes", "mel_prepare_weights", "mel_transpose_f32", "mel_episode_refill", "mel_abi_sizeof", "mel_radius_graph", "mel_gat_forward", "mel_gat_backward", "mel_pool_forward", "mel_pool_backward",
-           "mel_gemm_bf16", "mel_convert_bf16", "mel_hldgn_forward_envs", "mel_hldgn_forward_envs_select", "mel_plan_pointers", "mel_select_action_envs", "mel_dgnr_forward", "mel_dgnr_forward_agents", "mel_gemm_f32", "mel_gemm_f32_t", "mel_gemm_f32_splitk", "mel_gemm_f32_split", "mel_replay_sample", "mel_adam_step", "mel_workspace_bytes", "mel_workspace_bytes_agents", "mel_ldgn_forward_agents",
+           "mel_gemm_bf16", "mel_convert_bf16", "mel_hldgn_forward_envs", "mel_hldgn_forward_envs_select", "mel_plan_pointers", "mel_select_action_envs", "mel_dgnr_forward", "mel_dgnr_forward_agents", "mel_gemm_f32", "mel_gemm_f32_t", "mel_gemm_f32_splitk", "mel_gemm_f32_split", "mel_replay_sample", "mel_replay_sample_prio", "mel_replay_update_priority", "mel_adam_step", "mel_workspace_bytes", "mel_workspace_bytes_agents", "mel_ldgn_forward_agents",
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
@@ -88,6 +88,12 @@ class MelRoundReplay(C.Structure):
 class MelReplayBatch(C.Structure):
     _fields_ = [("obs", C.c_void_p), ("boot_obs", C.c_void_p), ("act", C.c_void_p), ("ret", C.c_void_p), ("boot_w", C.c_void_p),
                 ("env", C.c_void_p), ("slot", C.c_void_p), ("agent", C.c_void_p), ("nb_sibling", C.c_void_p)]
+
+
+class MelReplayPriority(C.Structure):
+    _fields_ = [("prio", C.c_void_p), ("rec_sum", C.c_void_p), ("prefix", C.c_void_p), ("seen", C.c_void_p),
+                ("max_prio", C.c_void_p), ("min_prio", C.c_void_p), ("alpha", C.c_double), ("beta", C.c_double),
+                ("weight_norm", C.c_int32), ("reserved", C.c_int32)]
 
 
 ADAM_MAX_TENSORS = 64
@@ -243,6 +249,11 @@ def load(build_if_missing: bool = True):
     lib.mel_replay_sample.restype = i32
     lib.mel_replay_sample.argtypes = [C.POINTER(MelRoundReplay), i64, i32, i32, i32, C.POINTER(C.c_float), C.c_uint64, vp, vp,
                                       C.POINTER(MelReplayBatch), vp]
+    lib.mel_replay_sample_prio.restype = i32
+    lib.mel_replay_sample_prio.argtypes = [C.POINTER(MelRoundReplay), C.POINTER(MelReplayPriority), i64, i32, i32, i32,
+                                           C.POINTER(C.c_float), C.c_uint64, vp, C.POINTER(MelReplayBatch), vp, vp]
+    lib.mel_replay_update_priority.restype = i32
+    lib.mel_replay_update_priority.argtypes = [C.POINTER(MelReplayPriority), i64, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.mel_env_observe.restype = i32
     lib.mel_env_observe.argtypes = [E, vp, i64, O, vp]
     lib.mel_mpr_sets.restype = i32

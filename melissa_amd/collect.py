@@ -489,7 +489,8 @@ class MultiAgentCollector(Collector):
 
     * ``env``: a :class:`melissa_amd.env.HipGraphVectorEnv` (the vector env of the scripts' ``DummyVectorEnv([...])``);
       ``agents_num`` must be its node count.
-    * ``buffer``: a :class:`melissa_amd.replay.RoundReplay` or None.  The reference routes every agent's transition into one of
+    * ``buffer``: a :class:`melissa_amd.replay.RoundReplay`, a :class:`melissa_amd.replay.PrioritizedRoundReplay` (the scripts'
+      ``--prio-buffer``: ``PrioritizedVectorReplayBuffer``, multi_agent_collector.py:60-65) or None.  The reference routes every agent's transition into one of
       ``env_num * agents_num`` sub-buffers and holds it back until the agent's next observation arrives
       (multi_agent_collector.py:229-271); here a whole env round is one record and ``RoundReplay.export_transitions()``
       yields the same transitions with the reference's ``buffer_id = env * agents_num + agent``.
@@ -533,6 +534,8 @@ class MultiAgentCollector(Collector):
         if self.buffer is not None:
             self.buffer.cursor.zero_()
             self.buffer.episode.fill_(-1)
+            if hasattr(self.buffer, "reset_priorities"):    # PrioritizedRoundReplay: priorities, seen, max_prio / min_prio too
+                self.buffer.reset_priorities()
 
     def reset_env(self, gym_reset_kwargs=None) -> None:
         """(the reference resets all envs after an n_episode collect; the device envs reset themselves at every episode end)"""
@@ -561,7 +564,8 @@ class CollectiveExperienceCollector(MultiAgentCollector):
     ``active_one_hop_neighbors``.  So the buffer must record neighbours: ``buffer=None`` creates a
     ``RoundReplay(neighbours=True)`` of ``buffer_rounds`` records per env (1: the reference's default
     ``VectorReplayBuffer(env_num * agents_num, env_num * agents_num)`` holds one transition per sub-buffer); a given
-    :class:`melissa_amd.replay.RoundReplay` without neighbours raises.  Everything else is :class:`MultiAgentCollector`."""
+    :class:`melissa_amd.replay.RoundReplay` without neighbours raises; a ``PrioritizedRoundReplay(neighbours=True)`` is accepted
+    like the reference's prioritized buffer (:60-62).  Everything else is :class:`MultiAgentCollector`."""
 
     def __init__(self, agents_num, buffer=None, buffer_rounds: int = 1, **kwargs):
         from .replay import RoundReplay

@@ -1139,9 +1139,72 @@ __device__ __forceinline__ int replay_pairs(const ReplaySampleArgs& a, int rec) 
     return c;
 }
 
+// The part of a sample both samplers share (the uniform one below, the prioritized one of replay_prio.hpp): the counter-based
+// draw, what follows the pick of (env e, slot k, agent) - the n-step walk, the per-sample outputs - and the observation copies.
+struct ReplayPicks { int env[1024], slot[1024], agent[1024], boot[1024]; };      // (LDS: the picks the copy loop reads)
+
+__device__ __forceinline__ unsigned long long replay_draw_bits(unsigned long long seed, unsigned long long draw, int tid) {
+    unsigned long long z = seed + draw * 0x9E3779B97F4A7C15ull + (unsigned long long)(tid + 1) * 0xD1B54A32D192ED03ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// sample `tid` = (e, k, agent); picked = false (an empty replay): e = k = agent = 0, ret 0, boot_w 1
+__device__ __forceinline__ void replay_emit_sample(const ReplaySampleArgs& a, int tid, bool picked, int e, int k, int agent, ReplayPicks& s) {
+    const int K = a.rp.capacity;
+    int boot = 0;
+    float ret = 0.f, bw = 1.f;
+    if (picked) {
+        // the n-step walk (replay.RoundReplay.sample's loop, same operation order in fp32)
+        const int filled = min(a.rp.cursor[e], K), newest = (int)(((long long)a.rp.cursor[e] - 1) % K);
+        const int ep0 = a.rp.episode[(size_t)e * K + k];
+        const int aw = agent >> 6;
+        const unsigned long long abit = 1ull << (agent & 63);
+        bool alive = true;
+        int kk = k;
+        boot = k;
+        for (int j = 0; j < a.n_step; ++j) {
+            const size_t rec = (size_t)e * K + kk;
+            const bool ok = alive && a.rp.episode[rec] == ep0 && (a.rp.acted[rec * a.W + aw] & abit) && kk < filled;
+            if (ok) {
+                ret = ret + a.disc[j] * a.rp.rew[rec * a.n + agent];
+                boot = kk;
+                bw = a.disc[j + 1];
+            }
+            const bool finished = ok && (a.rp.done[rec * a.W + aw] & abit);
+            if (finished) bw = 0.f;
+            alive = ok && !finished && kk != newest;
+            kk = kk + 1 == K ? 0 : kk + 1;
+        }
+    }
+    s.env[tid] = e, s.slot[tid] = k, s.agent[tid] = agent, s.boot[tid] = boot;
+    a.out.env[tid] = e, a.out.slot[tid] = k, a.out.agent[tid] = agent;
+    a.out.act[tid] = (long long)a.rp.act[((size_t)e * K + k) * a.n + agent];
+    a.out.ret[tid] = ret, a.out.boot_w[tid] = bw;
+    if (a.out.nb_sibling) {             // policies/n_dgn.py:36-47: siblings restricted to the one-hop set (+ the agent)
+        const size_t rec = (size_t)e * K + k;
+        for (int w = 0; w < a.W; ++w) {
+            const unsigned long long self = w == (agent >> 6) ? 1ull << (agent & 63) : 0ull;
+            a.out.nb_sibling[(size_t)tid * a.W + w] = a.rp.acted[rec * a.W + w] & (a.rp.active_nb[(rec * a.n + agent) * a.W + w] | self);
+        }
+    }
+}
+
+// all 1 024 threads, after a __syncthreads() behind the picks: obs / boot_obs rows = the record's obs_matrix | agent id
+__device__ __forceinline__ void replay_copy_obs(const ReplaySampleArgs& a, int tid, const ReplayPicks& s) {
+    const int K = a.rp.capacity, width = 8 * a.n, row = width + 1;
+    for (int i = tid; i < a.batch * row; i += 1024) {
+        const int sidx = i / row, c = i - sidx * row;
+        const size_t base = (size_t)s.env[sidx] * K;
+        a.out.obs[i] = c < width ? a.rp.obs[(base + s.slot[sidx]) * width + c] : (float)s.agent[sidx];
+        a.out.boot_obs[i] = c < width ? a.rp.obs_next[(base + s.boot[sidx]) * width + c] : (float)s.agent[sidx];
+    }
+}
+
 __global__ __launch_bounds__(1024) void replay_sample_kernel(ReplaySampleArgs a) {
     __shared__ int wave_tot[16];
-    __shared__ int s_env[1024], s_slot[1024], s_agent[1024], s_boot[1024];
+    __shared__ ReplayPicks picks;
     const int tid = threadIdx.x, K = a.rp.capacity, BK = a.B * K;
     const int lane = tid & 63, wv = tid >> 6;
     // (1) pair counts of consecutive records by consecutive threads (coalesced, sixteen chunks of 1 024 records in flight per
@@ -1184,13 +1247,9 @@ __global__ __launch_bounds__(1024) void replay_sample_kernel(ReplaySampleArgs a)
     __syncthreads();
     const unsigned long long draw = *a.counter;
     if (tid < a.batch) {
-        int e = 0, k = 0, agent = 0, boot = 0;
-        float ret = 0.f, bw = 1.f;
+        int e = 0, k = 0, agent = 0;
         if (total > 0) {
-            unsigned long long z = a.seed + draw * 0x9E3779B97F4A7C15ull + (unsigned long long)(tid + 1) * 0xD1B54A32D192ED03ull;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-            z ^= z >> 31;
+            const unsigned long long z = replay_draw_bits(a.seed, draw, tid);
             const int pick = (int)(((z >> 32) * (unsigned long long)total) >> 32);       // uniform in [0, total)
             int l = 0, h = BK;                             // last record whose prefix is <= pick (records without pairs share
             while (h - l > 1) {                            // their successor's prefix and are skipped)
@@ -1208,72 +1267,80 @@ __global__ __launch_bounds__(1024) void replay_sample_kernel(ReplaySampleArgs a)
                 agent = 64 * w + __ffsll((long long)m) - 1;
                 break;
             }
-            // the n-step walk (replay.RoundReplay.sample's loop, same operation order in fp32)
-            const int filled = min(a.rp.cursor[e], K), newest = (int)(((long long)a.rp.cursor[e] - 1) % K);
-            const int ep0 = a.rp.episode[(size_t)e * K + k];
-            const int aw = agent >> 6;
-            const unsigned long long abit = 1ull << (agent & 63);
-            bool alive = true;
-            int kk = k;
-            boot = k;
-            for (int j = 0; j < a.n_step; ++j) {
-                const size_t rec = (size_t)e * K + kk;
-                const bool ok = alive && a.rp.episode[rec] == ep0 && (a.rp.acted[rec * a.W + aw] & abit) && kk < filled;
-                if (ok) {
-                    ret = ret + a.disc[j] * a.rp.rew[rec * a.n + agent];
-                    boot = kk;
-                    bw = a.disc[j + 1];
-                }
-                const bool finished = ok && (a.rp.done[rec * a.W + aw] & abit);
-                if (finished) bw = 0.f;
-                alive = ok && !finished && kk != newest;
-                kk = kk + 1 == K ? 0 : kk + 1;
-            }
         }
-        s_env[tid] = e, s_slot[tid] = k, s_agent[tid] = agent, s_boot[tid] = boot;
-        a.out.env[tid] = e, a.out.slot[tid] = k, a.out.agent[tid] = agent;
-        a.out.act[tid] = (long long)a.rp.act[((size_t)e * K + k) * a.n + agent];
-        a.out.ret[tid] = ret, a.out.boot_w[tid] = bw;
-        if (a.out.nb_sibling) {             // policies/n_dgn.py:36-47: siblings restricted to the one-hop set (+ the agent)
-            const size_t rec = (size_t)e * K + k;
-            for (int w = 0; w < a.W; ++w) {
-                const unsigned long long self = w == (agent >> 6) ? 1ull << (agent & 63) : 0ull;
-                a.out.nb_sibling[(size_t)tid * a.W + w] = a.rp.acted[rec * a.W + w] & (a.rp.active_nb[(rec * a.n + agent) * a.W + w] | self);
-            }
-        }
+        replay_emit_sample(a, tid, total > 0, e, k, agent, picks);
     }
     __syncthreads();
-    const int width = 8 * a.n, row = width + 1;
-    for (int i = tid; i < a.batch * row; i += 1024) {
-        const int sidx = i / row, c = i - sidx * row;
-        const size_t base = (size_t)s_env[sidx] * K;
-        a.out.obs[i] = c < width ? a.rp.obs[(base + s_slot[sidx]) * width + c] : (float)s_agent[sidx];
-        a.out.boot_obs[i] = c < width ? a.rp.obs_next[(base + s_boot[sidx]) * width + c] : (float)s_agent[sidx];
-    }
+    replay_copy_obs(a, tid, picks);
     if (tid == 0) *a.counter = draw + 1;
 }
 
-mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int32_t n_nodes, int32_t batch, int32_t n_step,
-                             const float* discount, uint64_t seed, uint64_t* draw_counter, int32_t* scratch,
-                             const mel_replay_batch* out, void* stream) {
-    if (!replay || !discount || !draw_counter || !scratch || !out) return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: null argument");
+#include "replay_prio.hpp"
+
+// argument checks + launch arguments both samplers share (`who` names the entry point in the messages)
+static mel_status replay_sample_args(ReplaySampleArgs& a, const char* who, const mel_round_replay* replay, int64_t n_envs, int32_t n_nodes,
+                                     int32_t batch, int32_t n_step, const float* discount, uint64_t seed, uint64_t* draw_counter,
+                                     const mel_replay_batch* out) {
     if (replay->capacity < 1 || !replay->obs || !replay->obs_next || !replay->acted || !replay->done || !replay->act || !replay->rew ||
         !replay->episode || !replay->cursor)
         return fail(MEL_ERR_INVALID_ARG, "incomplete replay block");
     if (!out->obs || !out->boot_obs || !out->act || !out->ret || !out->boot_w || !out->env || !out->slot || !out->agent)
         return fail(MEL_ERR_INVALID_ARG, "incomplete replay batch");
     if (out->nb_sibling && !replay->active_nb)
-        return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: nb_sibling needs a replay that records active_nb");
+        return fail(MEL_ERR_INVALID_ARG, "%s: nb_sibling needs a replay that records active_nb", who);
     if (n_envs < 1 || n_nodes < 1 || n_nodes > MEL_MAX_NODES || batch < 1 || batch > 1024 || n_step < 1 || n_step > MEL_REPLAY_MAX_NSTEP ||
         n_envs * (int64_t)replay->capacity > (1ll << 24))
-        return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: batch in [1, 1024], n_step in [1, %d], n_envs * capacity <= 2^24", MEL_REPLAY_MAX_NSTEP);
-    clear_stale_error();
-    ReplaySampleArgs a{};
+        return fail(MEL_ERR_INVALID_ARG, "%s: batch in [1, 1024], n_step in [1, %d], n_envs * capacity <= 2^24", who, MEL_REPLAY_MAX_NSTEP);
     a.rp = *replay, a.out = *out, a.B = (int)n_envs, a.n = n_nodes, a.W = MEL_SET_WORDS(n_nodes), a.batch = batch, a.n_step = n_step;
     for (int j = 0; j <= n_step; ++j) a.disc[j] = discount[j];
-    a.seed = seed, a.counter = reinterpret_cast<unsigned long long*>(draw_counter), a.prefix = scratch;
+    a.seed = seed, a.counter = reinterpret_cast<unsigned long long*>(draw_counter);
+    return MEL_OK;
+}
+
+mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int32_t n_nodes, int32_t batch, int32_t n_step,
+                             const float* discount, uint64_t seed, uint64_t* draw_counter, int32_t* scratch,
+                             const mel_replay_batch* out, void* stream) {
+    if (!replay || !discount || !draw_counter || !scratch || !out) return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample: null argument");
+    ReplaySampleArgs a{};
+    if (mel_status st = replay_sample_args(a, "mel_replay_sample", replay, n_envs, n_nodes, batch, n_step, discount, seed, draw_counter, out))
+        return st;
+    a.prefix = scratch;
+    clear_stale_error();
     MEL_LAUNCH(replay_sample_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
     return check_launch("replay_sample");
+}
+
+mel_status mel_replay_sample_prio(const mel_round_replay* replay, const mel_replay_priority* priority, int64_t n_envs, int32_t n_nodes,
+                                  int32_t batch, int32_t n_step, const float* discount, uint64_t seed, uint64_t* draw_counter,
+                                  const mel_replay_batch* out, float* weight, void* stream) {
+    if (!replay || !discount || !draw_counter || !out || !weight) return fail(MEL_ERR_INVALID_ARG, "mel_replay_sample_prio: null argument");
+    if (mel_status st = check_replay_priority(priority, "mel_replay_sample_prio")) return st;
+    ReplayPrioSampleArgs pa{};
+    if (mel_status st = replay_sample_args(pa.s, "mel_replay_sample_prio", replay, n_envs, n_nodes, batch, n_step, discount, seed,
+                                           draw_counter, out))
+        return st;
+    pa.pr = *priority, pa.weight = weight;
+    clear_stale_error();
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t records = n_envs * (int64_t)replay->capacity;
+    MEL_LAUNCH(replay_prio_refresh_kernel, dim3((unsigned)((records + 3) / 4)), dim3(256), 0, s, pa.s.rp, pa.pr, pa.s.B, pa.s.n, pa.s.W);
+    MEL_LAUNCH(replay_sample_prio_kernel, dim3(1), dim3(1024), 0, s, pa);
+    return check_launch("replay_sample_prio");
+}
+
+mel_status mel_replay_update_priority(const mel_replay_priority* priority, int64_t n_envs, int32_t capacity, int32_t n_nodes,
+                                      int32_t batch, const int64_t* env, const int64_t* slot, const int64_t* agent, const float* td,
+                                      void* stream) {
+    if (mel_status st = check_replay_priority(priority, "mel_replay_update_priority")) return st;
+    if (!env || !slot || !agent || !td) return fail(MEL_ERR_INVALID_ARG, "mel_replay_update_priority: env / slot / agent / td missing");
+    if (n_envs < 1 || capacity < 1 || n_nodes < 1 || n_nodes > MEL_MAX_NODES || batch < 1 || batch > 1024 ||
+        n_envs * (int64_t)capacity > (1ll << 24))
+        return fail(MEL_ERR_INVALID_ARG, "mel_replay_update_priority: batch in [1, 1024], n_envs * capacity <= 2^24");
+    clear_stale_error();
+    MEL_LAUNCH(replay_prio_update_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), *priority, (int)n_envs, capacity,
+               n_nodes, batch, reinterpret_cast<const long long*>(env), reinterpret_cast<const long long*>(slot),
+               reinterpret_cast<const long long*>(agent), td);
+    return check_launch("replay_update_priority");
 }
 
 mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool* graphs, const mel_episode_pool* pool,

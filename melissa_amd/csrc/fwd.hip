@@ -733,6 +733,7 @@ size_t mel_abi_sizeof(int32_t which) {
         case 10: return sizeof(mel_episode_stream);
         case 11: return sizeof(mel_replay_batch);
         case 12: return sizeof(mel_adam_tensors);
+        case 13: return sizeof(mel_replay_priority);
         default: return 0;
     }
 }

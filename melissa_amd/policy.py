@@ -114,7 +114,8 @@ class DQNPolicy(nn.Module):
     # ------------------------------------------------------------------ learning (autograd path)
     def learn(self, batch, grad_hook=None) -> dict:
         """One DQN update on ``batch`` = dict(obs, act, returns[, weight]).  ``grad_hook(model)`` runs
-        between backward and the optimizer step (the RCCL gradient all-reduce plugs in here)."""
+        between backward and the optimizer step (the RCCL gradient all-reduce plugs in here).  ``batch["td_error"]`` is set to
+        ``returns - q`` (what [3P] hands the prioritized buffer in ``batch.weight``)."""
         if self._target and self._iter % self._freq == 0:
             self.sync_weight()
         loss = self.loss_backward(batch)
@@ -134,8 +135,16 @@ class DQNPolicy(nn.Module):
             q = logits[torch.arange(len(act), device=logits.device), act]
             returns = torch.as_tensor(batch["returns"], device=logits.device, dtype=q.dtype).flatten()
             td = returns - q
-            loss = torch.nn.functional.huber_loss(q, returns) if self._clip_loss_grad else td.pow(2).mean()
+            weight = batch.get("weight") if isinstance(batch, dict) else None
+            if self._clip_loss_grad:                 # ([3P] DQNPolicy.learn: the Huber form leaves the weight unused)
+                loss = torch.nn.functional.huber_loss(q, returns)
+            elif weight is None:
+                loss = td.pow(2).mean()
+            else:                                    # prioritized replay's importance weights: (td^2 * weight).mean()
+                loss = (td.pow(2) * torch.as_tensor(weight, device=logits.device, dtype=td.dtype)).mean()
             loss.backward()
+        if isinstance(batch, dict):
+            batch["td_error"] = td.detach()          # what [3P] leaves in batch.weight for PrioritizedReplayBuffer.update_weight
         return loss.detach()
 
 
@@ -196,8 +205,10 @@ class DGNPolicy(DQNPolicy):
                 else:
                     loss = (td.pow(2) * torch.as_tensor(weight, device=dev, dtype=td.dtype)).mean()
             loss.backward()
-        if isinstance(batch, dict) and "obs_matrix" not in batch:
-            batch["weight"] = td.detach()            # prio-buffer hook, dgn.py:66
+        if isinstance(batch, dict):
+            batch["td_error"] = td.detach()          # (device tensor, both forms: the prioritized replay's write-back reads it)
+            if "obs_matrix" not in batch:
+                batch["weight"] = td.detach()        # prio-buffer hook, dgn.py:66
         return loss.detach()
 
     @staticmethod
@@ -247,6 +258,7 @@ class NDGNPolicy(DGNPolicy):
                 rows["weight"] = batch["weight"]
             loss = super().loss_backward(rows)
             batch["weight"] = rows["weight"]                    # prio-buffer hook, n_dgn.py:67
+            batch["td_error"] = rows["td_error"]
             return loss
         return super().loss_backward(batch)
 

@@ -7,6 +7,8 @@ sub-buffers, waiting for the agent's next observation before the record is compl
 (``mel_round_replay`` in include/melissa_hip.h) written by ``mel_env_round``: all of the round's agents share
 ``obs`` / ``obs_next`` (they observe the same obs_matrix, graph.py:186-188), so a transition is
 ``(record, agent)`` and an agent's trajectory is the run of consecutive records of its env in which it acts.
+:class:`PrioritizedRoundReplay` samples those transitions by priority (the scripts' ``--prio-buffer``: [3P]
+``PrioritizedVectorReplayBuffer``, l_dgn.py:169-176).
 """
 from __future__ import annotations
 
@@ -106,6 +108,11 @@ class RoundReplay:
         target = (u * bits.sum(1)).floor().long().clamp(max=self.n - 1)
         order = torch.cumsum(bits.long(), dim=1) - 1
         agent = ((order == target[:, None]) & bits).float().argmax(dim=1)
+        return self._walk_host(e, k, agent, n_step, gamma)
+
+    def _walk_host(self, e: torch.Tensor, k: torch.Tensor, agent: torch.Tensor, n_step: int, gamma: float) -> dict:
+        """The n-step walk and the batch of the picked transitions (env e, slot k, agent): what follows the pick in ``sample``."""
+        dev, batch_size, valid = self.obs.device, e.numel(), self._valid_slots()
         ret = torch.zeros(batch_size, device=dev)
         boot_w = torch.ones(batch_size, device=dev)
         alive = torch.ones(batch_size, dtype=torch.bool, device=dev)
@@ -132,9 +139,10 @@ class RoundReplay:
         return out
 
 
-    def _sample_device(self, batch_size: int, n_step: int, gamma: float, generator):
+    def _device_batch(self, batch_size: int, n_step: int, gamma: float, generator):
+        """Output tensors of a one-launch sample + what both samplers pass to the library: (out, MelReplayBatch, discount, seed)."""
         import ctypes as C
-        dev, lib = self.obs.device, _lib.load()
+        dev = self.obs.device
         if not getattr(self, "_nonempty", False):               # (one host read, until the first record is seen)
             if int(self.cursor.max()) < 1:
                 raise ValueError("cannot sample from an empty replay: run the collect loop first")
@@ -155,6 +163,12 @@ class RoundReplay:
             setattr(b, name, t.data_ptr())
         disc = (C.c_float * (n_step + 1))(*[gamma ** j for j in range(n_step + 1)])
         seed = (generator.initial_seed() if generator is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        return out, b, disc, seed
+
+    def _sample_device(self, batch_size: int, n_step: int, gamma: float, generator):
+        import ctypes as C
+        dev, lib = self.obs.device, _lib.load()
+        out, b, disc, seed = self._device_batch(batch_size, n_step, gamma, generator)
         _lib.check(lib.mel_replay_sample(C.byref(self.struct), self.B, self.n, batch_size, n_step, disc, seed,
                                          self._draws.data_ptr(), self._prefix.data_ptr(), C.byref(b),
                                          _lib.current_stream_ptr(dev)), "mel_replay_sample")
@@ -206,6 +220,113 @@ class RoundReplay:
         return {name: t.cpu().numpy() for name, t in out.items()}
 
 
+class PrioritizedRoundReplay(RoundReplay):
+    """:class:`RoundReplay` sampled by priority: the counterpart of [3P] tianshou 1.0.0 ``PrioritizedVectorReplayBuffer(total_size,
+    buffer_num, alpha=, beta=)``, which the reference's six scripts switch to with ``--prio-buffer --alpha 0.6 --beta 0.4``
+    (common.py:52,64-65, l_dgn.py:169-176).  Parity unpinned: tianshou is restated from its published behaviour.
+
+    One priority per transition (env, slot, acting agent), one sum over the whole buffer: ``prio`` [B, K, N] holds ``p ** alpha``
+    (0 for agents that did not act and for slots not yet filled), ``max_prio = min_prio = 1``.
+
+    * a new transition gets ``max_prio ** alpha`` - lazily, by the first ``sample`` that sees its record (``seen`` [B] remembers
+      ``cursor`` at the last sample; ``max_prio`` only changes in ``update_weight``, which always follows a ``sample``, so the value
+      is the one upstream's ``add`` would have written, and the collect loop's launch stays as it is);
+    * ``sample``: ``scalar = u * prio.sum()``, the first transition in buffer order whose inclusive float64 prefix sum exceeds
+      it, with replacement; ``weight = (prio[index] / min_prio) ** -beta`` (upstream's simplified form: the numerator is already
+      ``p ** alpha``, the denominator the raw ``min_prio``), divided by its maximum over the batch when ``weight_norm``;
+    * ``update_weight(batch, td)`` ([3P] ``BasePolicy.post_process_fn`` -> ``update_weight(indices, batch.weight)``): ``p = |td| +
+      eps`` in float32, ``prio = p ** alpha``, ``max_prio`` / ``min_prio`` follow ``p``; an index sampled twice keeps the LAST.
+
+    On the GPU these are three launches with no host value in the loop (``mel_replay_sample_prio``: refresh + sample;
+    ``mel_replay_update_priority``), so a captured update contains them.  Host tensors take the torch formulation of the same rules
+    (float64 cumsum + searchsorted, torch's own random stream)."""
+
+    def __init__(self, n_envs: int, n_nodes: int, capacity: int, device, neighbours: bool = False, alpha: float = 0.6,
+                 beta: float = 0.4, weight_norm: bool = True):
+        if alpha < 0 or beta < 0:
+            raise ValueError(f"alpha={alpha} and beta={beta} must be >= 0")
+        super().__init__(n_envs, n_nodes, capacity, device, neighbours=neighbours)
+        self.alpha, self.beta, self.weight_norm = float(alpha), float(beta), bool(weight_norm)
+        dev = self.obs.device
+        self.prio = torch.zeros(n_envs, capacity, n_nodes, dtype=torch.float32, device=dev)
+        self.seen = torch.zeros(n_envs, dtype=torch.int32, device=dev)
+        self.max_prio = torch.ones(1, dtype=torch.float32, device=dev)
+        self.min_prio = torch.ones(1, dtype=torch.float32, device=dev)
+        self._rec_sum = torch.zeros(n_envs * capacity, dtype=torch.float64, device=dev)
+        self._prio_prefix = torch.zeros(n_envs * capacity + 1, dtype=torch.float64, device=dev)
+        p = _lib.MelReplayPriority()
+        p.prio, p.rec_sum, p.prefix, p.seen = self.prio.data_ptr(), self._rec_sum.data_ptr(), self._prio_prefix.data_ptr(), self.seen.data_ptr()
+        p.max_prio, p.min_prio = self.max_prio.data_ptr(), self.min_prio.data_ptr()
+        p.alpha, p.beta, p.weight_norm = self.alpha, self.beta, int(self.weight_norm)
+        self.prio_struct = p
+
+    def reset_priorities(self) -> None:
+        """Back to the state of construction (the collectors' ``reset_buffer`` calls this with the write cursors)."""
+        self.prio.zero_()
+        self.seen.zero_()
+        self.max_prio.fill_(1.0)
+        self.min_prio.fill_(1.0)
+
+    def refresh(self) -> None:
+        """Host form of the lazy initialisation (the device does it inside ``sample``): records written since the last sample get
+        ``max_prio ** alpha`` for their acting agents, 0 elsewhere."""
+        cur, seen = self.cursor.long(), self.seen.long()
+        written = cur - seen
+        d = (torch.arange(self.K, device=cur.device)[None, :] - (seen % self.K)[:, None]) % self.K           # [B, K]
+        fresh = (written[:, None] >= self.K) | (written[:, None] < 0) | (d < written[:, None])
+        init = torch.pow(self.max_prio, self.alpha)                                                        # float32, like powf
+        new = torch.where(self._members(self.acted), init, torch.zeros((), device=cur.device))
+        self.prio.copy_(torch.where(fresh[:, :, None], new, self.prio))
+        self.seen.copy_(self.cursor)
+
+    def sample(self, batch_size: int, n_step: int, gamma: float, generator: torch.Generator | None = None):
+        """:meth:`RoundReplay.sample` by priority; adds ``weight`` [bs] float32."""
+        dev = self.obs.device
+        if dev.type == "cuda":
+            import ctypes as C
+            out, b, disc, seed = self._device_batch(batch_size, n_step, gamma, generator)
+            out["weight"] = torch.empty(batch_size, device=dev)
+            _lib.check(_lib.load().mel_replay_sample_prio(
+                C.byref(self.struct), C.byref(self.prio_struct), self.B, self.n, batch_size, n_step, disc, seed,
+                self._draws.data_ptr(), C.byref(b), out["weight"].data_ptr(), _lib.current_stream_ptr(dev)), "mel_replay_sample_prio")
+            return out
+        self.refresh()
+        incl = torch.cumsum(self.prio.double().flatten(), 0)
+        total = incl[-1]
+        if float(total) <= 0:
+            raise ValueError("cannot sample from an empty replay: run the collect loop first")
+        scalar = torch.rand(batch_size, dtype=torch.float64, device=dev, generator=generator) * total
+        idx = torch.searchsorted(incl, scalar, right=True).clamp(max=incl.numel() - 1)
+        e, k, agent = idx // (self.K * self.n), (idx // self.n) % self.K, idx % self.n
+        out = self._walk_host(e, k, agent, n_step, gamma)
+        w = (self.prio[e, k, agent].double() / self.min_prio.double()) ** (-self.beta)
+        out["weight"] = (w / w.max() if self.weight_norm else w).float()
+        return out
+
+    def update_weight(self, batch: dict, td: torch.Tensor) -> None:
+        """``batch``: the ``env`` / ``slot`` / ``agent`` of a sampled batch; ``td``: its TD error [bs] (any sign; a device tensor on the
+        GPU: no host synchronisation)."""
+        e, k, a = batch["env"], batch["slot"], batch["agent"]
+        dev = self.obs.device
+        td = td.detach().to(torch.float32).flatten()
+        if td.numel() != e.numel():
+            raise ValueError(f"update_weight: {td.numel()} TD errors for {e.numel()} samples")
+        if dev.type == "cuda":
+            import ctypes as C
+            td = td.contiguous()
+            _lib.check(_lib.load().mel_replay_update_priority(
+                C.byref(self.prio_struct), self.B, self.K, self.n, td.numel(), e.data_ptr(), k.data_ptr(), a.data_ptr(),
+                td.data_ptr(), _lib.current_stream_ptr(dev)), "mel_replay_update_priority")
+            return
+        p = td.abs() + torch.finfo(torch.float32).eps
+        key = (e * self.K + k) * self.n + a
+        uniq, inv = torch.unique(key, return_inverse=True)
+        last = torch.zeros_like(uniq).scatter_reduce(0, inv, torch.arange(key.numel()), "amax", include_self=False)
+        self.prio.view(-1)[uniq] = torch.pow(p[last], self.alpha)
+        self.max_prio.copy_(torch.maximum(self.max_prio, p.max()))
+        self.min_prio.copy_(torch.minimum(self.min_prio, p.min()))
+
+
 class DQNLearner:
     """n-step DQN update over a :class:`RoundReplay` (the learn half of the reference's training loop,
     l_dgn.py:246-261 -> [3P] DQNPolicy.process_fn / learn): target = ret + boot_w * max_a Q_target(boot_obs)
@@ -233,13 +354,43 @@ class DQNLearner:
                 best = q_next.max(dim=1).values
             returns = b["ret"] + b["boot_w"] * best
         # (boot_obs / ret / boot_w: what `returns` was built from - tests recompute it through the target network)
-        return dict(obs=b["obs"], act=b["act"], returns=returns, boot_obs=b["boot_obs"], ret=b["ret"], boot_w=b["boot_w"])
+        out = dict(obs=b["obs"], act=b["act"], returns=returns, boot_obs=b["boot_obs"], ret=b["ret"], boot_w=b["boot_w"])
+        return self._with_priority_keys(out, b)
+
+    @staticmethod
+    def _with_priority_keys(out: dict, b: dict) -> dict:
+        """A batch sampled from a :class:`PrioritizedRoundReplay` also carries its importance ``weight`` (the loss uses it) and the
+        ``env`` / ``slot`` / ``agent`` its priorities are written back to."""
+        if "weight" in b:
+            out.update(weight=b["weight"], env=b["env"], slot=b["slot"], agent=b["agent"])
+        return out
+
+    def write_back(self, batch: dict) -> None:
+        """Prioritized replay only: the TD error ``loss_backward`` left in ``batch`` becomes the sampled transitions' priorities
+        ([3P] ``post_process_fn``) - between backward and the optimizer step, eagerly and inside a captured update's graph."""
+        if "weight" in batch and hasattr(self.replay, "update_weight"):
+            self.replay.update_weight(batch, batch["td_error"])
+
+    def _learn(self, batch: dict) -> dict:
+        """``policy.learn`` on a copy of ``batch`` with the priority write-back ahead of the gradient hook; the TD error ends up in
+        ``last_batch["td_error"]``."""
+        work = dict(batch)
+
+        def hook(model):
+            self.write_back(work)
+            if self.grad_hook is not None:
+                self.grad_hook(model)
+
+        out = self.policy.learn(work, grad_hook=hook if "weight" in work else self.grad_hook)
+        if "td_error" in work:
+            self.last_batch["td_error"] = work["td_error"]
+        return out
 
     def step(self) -> dict:
         if self.captured is not None:
             return self.captured.step()
         self.last_batch = self.sample_batch()                                      # what the update regressed on (tests)
-        return self.policy.learn(dict(self.last_batch), grad_hook=self.grad_hook)
+        return self._learn(self.last_batch)
 
     def capture(self) -> "CapturedUpdate":
         """From now on ``step`` replays the update from HIP graphs (see :class:`CapturedUpdate`)."""
@@ -255,7 +406,7 @@ class CapturedUpdate:
     observations), so after two eager warm-up updates the whole chain is captured once:
 
         graph A   sample -> n-step targets (target network, HIP forward) -> zero_grad -> forward -> loss -> backward
-                  [-> gradients packed into the reducer's flat buffer]
+                  [-> priority write-back (PrioritizedRoundReplay)] [-> gradients packed into the reducer's flat buffer]
         eager     [one all-reduce of the flat buffer + division: RCCL stays outside the capture]
         graph B   [flat buffer unpacked into the gradients ->] optimizer step
 
@@ -291,6 +442,7 @@ class CapturedUpdate:
                 self._sync_target()
                 batch = L.sample_batch()
                 policy.loss_backward(batch)
+                L.write_back(batch)
                 if self.collective:
                     hook.pack(), hook.reduce(), hook.unpack()
                 adam_step(opt)
@@ -302,6 +454,7 @@ class CapturedUpdate:
         with torch.cuda.graph(self.graph_a):
             self.batch = L.sample_batch()
             self.loss = policy.loss_backward(self.batch)
+            L.write_back(self.batch)                        # (prioritized replay: the next replay samples by what this one wrote)
             if self.collective:
                 hook.pack()
             else:
@@ -363,9 +516,10 @@ class DGNLearner(DQNLearner):
             else:
                 best = q_next.max(dim=1).values
             returns = b["ret"] + b["boot_w"] * best
-        return dict(obs_matrix=self.replay.obs[e, k], act_all=self.replay.act[e, k].long(),
-                    sibling=self.replay._members(self.replay.acted[e, k]), returns=returns, boot_obs=b["boot_obs"], ret=b["ret"],
-                    boot_w=b["boot_w"], env=e, slot=k)
+        out = dict(obs_matrix=self.replay.obs[e, k], act_all=self.replay.act[e, k].long(),
+                   sibling=self.replay._members(self.replay.acted[e, k]), returns=returns, boot_obs=b["boot_obs"], ret=b["ret"],
+                   boot_w=b["boot_w"], env=e, slot=k)
+        return self._with_priority_keys(out, b)
 
     def row_form(self, batch: dict) -> dict:
         """The same batch in the reference's row form (what collective_experience_collector.py:70-80 records as ``info.indices``:
@@ -380,7 +534,7 @@ class DGNLearner(DQNLearner):
             return self.captured.step()
         batch = self.sample_batch()
         self.last_batch = dict(batch, **self.row_form(batch))
-        return self.policy.learn(dict(batch), grad_hook=self.grad_hook)
+        return self._learn(batch)
 
 
 class NDGNLearner(DGNLearner):
@@ -407,4 +561,4 @@ class NDGNLearner(DGNLearner):
         if self.captured is not None:
             return self.captured.step()
         self.last_batch = self.sample_batch()
-        return self.policy.learn(dict(self.last_batch), grad_hook=self.grad_hook)
+        return self._learn(self.last_batch)

@@ -54,7 +54,7 @@ def policy_and_learner(name: str):
 
 def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4, batch_size=32, n_step=4,
           gamma=0.99, lr=1e-3, target_update_freq=500, eps=0.1, replay_rounds=64, seed=9, backend=None, log=print,
-          probe=None, graphs=16, ring=16, capture_updates=None):
+          probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -62,12 +62,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     device episode stream: every reset draws a new (graph, source, interested set, movement seed) like World.reset.
     ``capture_updates``: replay the update from HIP graphs (``DQNLearner.capture``; DGN-R and N-DGN too: their dense sibling forms
     have static shapes, replay.DGNLearner / replay.NDGNLearner).  None = on unless a probe is attached; with several ranks the collective stays
-    eager between two graphs.  The capture takes two extra (real, untimed) updates first: ``warmup_updates`` in the result."""
+    eager between two graphs.  The capture takes two extra (real, untimed) updates first: ``warmup_updates`` in the result.
+    ``prio_buffer`` / ``alpha`` / ``beta``: the reference's ``--prio-buffer --alpha --beta`` (common.py:52,64-65): sample from a
+    :class:`melissa_amd.replay.PrioritizedRoundReplay` (each rank owns its buffer; nothing more is exchanged)."""
     import torch
     from . import launch, parallel
     from .collect import RoundLoop
     from .env import HipGraphVectorEnv, synthetic_graph_pool
-    from .replay import RoundReplay
+    from .replay import PrioritizedRoundReplay, RoundReplay
     if backend != "gloo":
         launch.check_rank_device()                             # exit 2 when LOCAL_RANK names a GPU this rank cannot see
     rank, local_rank, world = parallel.init_distributed(backend)
@@ -83,7 +85,10 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     graph_list = cached_graph_pool(n_nodes, graphs, 0) if graphs >= 4096 else synthetic_graph_pool(n_nodes, graphs, first_seed=0)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False)
-    replay = RoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours)
+    if prio_buffer:
+        replay = PrioritizedRoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours, alpha=alpha, beta=beta)
+    else:
+        replay = RoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours)
     # the rounds between two updates replay from one HIP graph (bit-identical to the eager launches: tests/test_gpu_round.py)
     loop = RoundLoop(venv, policy, seed=1000 + rank * envs, eps=eps, replay=replay, ring=ring,
                      use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update))
@@ -117,7 +122,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     checksum = float(torch.cat([p.detach().flatten() for p in net.parameters()]).double().sum())
     out = dict(rank=rank, world=world, model=model, updates=updates, seconds=dt, loss_first=losses[0],
                loss_last=losses[-1], decisions=c["decisions"], episodes=c["episodes"], errors=c["errors"],
-               param_checksum=checksum, updates_from_hip_graphs=captured,
+               param_checksum=checksum, updates_from_hip_graphs=captured, prio_buffer=bool(prio_buffer),
                # the capture's warm-up updates are REAL optimizer steps taken before the timed loop (they advance the policy's
                # iteration counter and the replay sampler's generator): a run with capture on has taken `updates +
                # warmup_updates` steps, `seconds` covers `updates` of them
@@ -131,7 +136,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     return out
 
 
-def main():
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="hl_dgn", choices=list(MODELS))
     ap.add_argument("--nodes", type=int, default=20)
@@ -145,7 +150,15 @@ def main():
     ap.add_argument("--capture-updates", choices=["auto", "on", "off"], default="auto",
                     help="replay the DQN update from HIP graphs (auto: on; the capture runs 2 extra untimed warm-up updates first, "
                          "reported as warmup_updates - compare on / off runs at equal total updates)")
-    a = ap.parse_args()
+    # the reference's names and defaults (common.py:52,64-65)
+    ap.add_argument("--prio-buffer", action="store_true", default=False, help="prioritized experience replay")
+    ap.add_argument("--alpha", type=float, default=0.6, help="prioritization exponent")
+    ap.add_argument("--beta", type=float, default=0.4, help="importance-weight exponent")
+    return ap
+
+
+def main():
+    a = arg_parser().parse_args()
     import os
     import sys
     from . import launch
@@ -154,7 +167,8 @@ def main():
         raise SystemExit(rc)
     train(model=a.model, n_nodes=a.nodes, envs=a.envs, updates=a.updates, rounds_per_update=a.rounds_per_update,
           batch_size=a.batch_size, backend=a.backend, graphs=a.graphs,
-          capture_updates={"auto": None, "on": True, "off": False}[a.capture_updates])
+          capture_updates={"auto": None, "on": True, "off": False}[a.capture_updates],
+          prio_buffer=a.prio_buffer, alpha=a.alpha, beta=a.beta)
 
 
 if __name__ == "__main__":
