@@ -512,8 +512,10 @@ typedef struct mel_episode_pool {
  * device-resident dataset (mel_graph_pool: positions + adjacency masks of the G graphs that stand for
  * graph_topologies/training_N/*.pickle, core.py:165-175,450-452).  Each call also runs GraphEnv.reset + World.reset
  * for the new slots into the pool's snapshot batch (same code as mel_env_reset), so an ending episode loads its
- * successor's state.  Not covered (use a host-sampled table): is_testing's fixed seed list, scripted_agents_ratio > 0
- * (a Generator.choice without replacement), a fixed graph that moves (its positions carry over between episodes).
+ * successor's state.  With scripted agents (n_scripted > 0) the env's generator also draws World._sample_scripted_agents'
+ * np_random.choice(N, n_scripted, replace=False) after the graph (core.py:197-215,395: Floyd's algorithm + the shuffle's
+ * draws; the source leaves the set).  Not covered (use a host-sampled table): is_testing's fixed seed list, a fixed graph
+ * that moves (its positions carry over between episodes); training mode with every node scripted is not playable.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct mel_graph_pool {
     int32_t n_graphs;
@@ -535,11 +537,16 @@ typedef struct mel_episode_stream {
     int32_t*  draw_graph;      /* [B, K] device scratch: graph index per slot (core.py:378)                     */
     int32_t*  work;            /* [1 + 2*B*K] device scratch: work-item count, then (pool slot, unused) pairs   */
     int32_t*  new_count;       /* [B]    device scratch                                                         */
+    int32_t   n_scripted;      /* scripted agents per episode: int(round(scripted_agents_ratio * N)) computed by the HOST
+                                * (Python's rounding, core.py:200); 0 = none, nothing more is drawn                      */
+    int32_t   reserved;
+    uint64_t* draw_scripted;   /* [B, K, MEL_SET_WORDS(N)] device scratch: the drawn set per slot, source included
+                                * (core.py:395); may be NULL when n_scripted == 0                                        */
 } mel_episode_stream;
 
 /* For every env b draw episodes produced[b], produced[b]+1, ... while the slot they go to is free - i.e. up to episode
  * ep_cursor[b] + ring - 2 (the episode the env is playing keeps its slot) - and at most max_new of them; fill their
- * pool slots (pos / one_hop / origin / interested / scripted = 0 / moves), run their reset into pool->snapshot, then
+ * pool slots (pos / one_hop / origin / interested / scripted / moves), run their reset into pool->snapshot, then
  * publish produced[b].  `discard` episodes are drawn and dropped first (the samplings the reference performs while an
  * env is CONSTRUCTED, so that streams line up with a reference run).  `pool` must have n_episodes == B*ring, device
  * arrays the library may WRITE, a snapshot batch of B*ring envs, and produced == stream->produced.  ep_cursor is read

@@ -137,7 +137,8 @@ class MelEpisodeStream(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("ring", C.c_int32), ("fixed_graph", C.c_int32), ("has_density", C.c_int32),
                 ("fixed_interest_density", C.c_double), ("pcg", C.c_void_p), ("pcg_half", C.c_void_p),
                 ("produced", C.c_void_p), ("draw_seed", C.c_void_p), ("draw_graph", C.c_void_p), ("work", C.c_void_p),
-                ("new_count", C.c_void_p)]
+                ("new_count", C.c_void_p), ("n_scripted", C.c_int32), ("reserved", C.c_int32),
+                ("draw_scripted", C.c_void_p)]
 
 
 ENV_ERR_MOVES_EXHAUSTED, ENV_ERR_NO_SELECTION, ENV_ERR_UNCOVERED_AGENT, ENV_ERR_EPISODE_UNDERRUN = 1, 2, 4, 8

@@ -1,12 +1,12 @@
 // Continuous episode supply: World.reset's sampling (graph_env/env/utils/core.py:343-395) on the device, bit for bit.
 //
 // Included by env.hip inside namespace mel (it calls env_reset / env_store).  Three launches per refill:
-//   episode_draw_kernel    one thread per env: the env's own generator (numpy Generator(PCG64)) draws episode_seed and
-//                          the graph for each free ring slot, in order                             core.py:372,378
+//   episode_draw_kernel    one thread per env: the env's own generator (numpy Generator(PCG64)) draws episode_seed, the
+//                          graph and the scripted set for each free ring slot, in order        core.py:372,378,395
 //   episode_fill_kernel    one wavefront per new episode: RandomState(episode_seed) (MT19937) draws movement seed, source,
 //                          interest density and the interested set; RandomState(movement_seed) fills the movement offsets;
-//                          the graph is copied from the packed dataset; GraphEnv.reset + World.reset run into the snapshot
-//                          batch                                                          core.py:381-394,316-319,398-437
+//                          the graph is copied from the packed dataset; the scripted set loses the source (:213-215);
+//                          GraphEnv.reset + World.reset run into the snapshot batch    core.py:381-394,316-319,398-437
 //   episode_publish_kernel produced[b] += new_count[b]
 //
 // numpy algorithms restated here (numpy/random/src: pcg64.h, mt19937.c, distributions.c, legacy):
@@ -17,6 +17,9 @@
 //   RandomState.randint   masked rejection: draw & mask until <= range
 //   RandomState.uniform   low + (high - low) * ((a >> 5) * 2^26 + (b >> 6)) / 2^53, a, b consecutive 32-bit outputs
 //   RandomState.choice(n, k, replace=False) = permutation(n)[:k]: Fisher-Yates from the top, j = random_interval(i)
+//   Generator.choice(n, k, replace=False)  (p None, n <= 10000): Floyd's algorithm - for j = n-k .. n-1 draw v in [0, j]
+//               and take v, or j when v is already taken - then a Fisher-Yates shuffle of the k results, i = k-1 .. 1, each
+//               one bounded draw in [0, i].  Both use the Lemire draw above (a range of 0 draws nothing).
 #pragma once
 
 namespace mel {
@@ -65,6 +68,19 @@ __device__ __forceinline__ uint32_t pcg64_bounded(Pcg64& g, uint32_t rng) {
     return (uint32_t)(m >> 32);
 }
 
+// World._sample_scripted_agents' draw (core.py:197-212): np_random.choice(n, size=k, replace=False) as a SET.  Floyd's hash
+// table is a membership test on the set itself, and the shuffle only reorders the k results: its draws are consumed, its
+// data movement cannot matter to a set.  Two words always (n <= MEL_MAX_NODES = 128); k == 0 draws nothing.
+__device__ __forceinline__ NodeSet<2> pcg64_choice_set(Pcg64& g, int n, int k) {
+    NodeSet<2> set = ns_zero<2>();
+    for (int j = n - k; j < n; ++j) {
+        const int v = (int)pcg64_bounded(g, (uint32_t)j);
+        set |= ns_bit<2>(ns_test(set, v) ? j : v);
+    }
+    for (int i = k - 1; i >= 1; --i) (void)pcg64_bounded(g, (uint32_t)i);
+    return set;
+}
+
 struct StreamArgs {
     mel_episode_stream st;
     mel_graph_pool graphs;
@@ -83,9 +99,11 @@ __global__ __launch_bounds__(256) void episode_draw_kernel(StreamArgs a) {
     g.inc_lo = a.st.pcg[4 * (size_t)b + 2], g.inc_hi = a.st.pcg[4 * (size_t)b + 3];
     g.has32 = a.st.pcg_half[2 * (size_t)b], g.half = a.st.pcg_half[2 * (size_t)b + 1];
     const uint32_t graph_rng = (uint32_t)(a.graphs.n_graphs - 1);
+    const int n = a.pool.n_nodes, k_scripted = a.st.n_scripted, words = MEL_SET_WORDS(n);
     for (int d = 0; d < a.discard; ++d) {                       // episodes the reference samples and throws away
         (void)pcg64_bounded(g, 999999999u);
         if (!a.st.fixed_graph) (void)pcg64_bounded(g, graph_rng);
+        if (k_scripted > 0) (void)pcg64_choice_set(g, n, k_scripted);
     }
     const int cur = a.env.scalars[(size_t)b * MEL_ENV_SCALARS + MEL_S_EP_CURSOR];
     const int first = a.st.produced[b];
@@ -94,6 +112,10 @@ __global__ __launch_bounds__(256) void episode_draw_kernel(StreamArgs a) {
         const int slot = b * K + (first + cnt) % K;
         a.st.draw_seed[slot] = pcg64_bounded(g, 999999999u);                                  // core.py:372
         a.st.draw_graph[slot] = a.st.fixed_graph ? 0 : (int)pcg64_bounded(g, graph_rng);      // core.py:377-379
+        if (k_scripted > 0) {                                                                 // core.py:395 (uniform branch)
+            const NodeSet<2> set = pcg64_choice_set(g, n, k_scripted);
+            for (int w = 0; w < words; ++w) a.st.draw_scripted[(size_t)slot * words + w] = set.w[w];
+        }
         const int w = atomicAdd(a.st.work, 1);
         a.st.work[1 + w] = slot;
         ++cnt;
@@ -261,7 +283,9 @@ __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
         if (lane == 0) {
             const_cast<int32_t*>(a.pool.origin)[slot] = origin;
             ns_store<W>(const_cast<uint64_t*>(a.pool.interested), slot, interested);
-            if (a.pool.scripted) ns_store<W>(const_cast<uint64_t*>(a.pool.scripted), slot, ns_zero<W>());      // scripted_agents_ratio == 0
+            if (a.st.n_scripted > 0)                           // the source is never scripted while ratio < 1  core.py:213-215
+                ns_store<W>(const_cast<uint64_t*>(a.pool.scripted), slot, ns_load<W>(a.st.draw_scripted, slot) & ~ns_bit<W>(origin));
+            else if (a.pool.scripted) ns_store<W>(const_cast<uint64_t*>(a.pool.scripted), slot, ns_zero<W>());      // scripted_agents_ratio == 0
         }
         // ---- movement_np_random = RandomState(movement_seed): step * uniform(-1, 1), x's then y's per move   :316-319,382
         if (a.env.dynamic_graph) {
@@ -319,8 +343,12 @@ static mel_status launch_episode_refill(const mel_episode_stream* st, const mel_
         return fail(MEL_ERR_INVALID_ARG, "graph pool of %d graphs x %d nodes for %d-node envs", graphs->n_graphs, graphs->n_nodes, env->n_nodes);
     if (st->fixed_graph && (graphs->n_graphs != 1 || env->dynamic_graph))
         return fail(MEL_ERR_UNSUPPORTED, "a fixed graph streams only when it is static (a moving fixed graph carries its positions over)");
-    if (env->is_testing || env->heuristic != MEL_HEURISTIC_NONE)
-        return fail(MEL_ERR_UNSUPPORTED, "the device sampler covers training mode without scripted agents");
+    if (env->is_testing) return fail(MEL_ERR_UNSUPPORTED, "the device sampler covers training mode (the evaluation schedule is a periodic table)");
+    // (n_scripted, not env->heuristic: a ratio without a heuristic is legal - scripted nodes then simply never act)
+    if (st->n_scripted < 0 || st->n_scripted > env->n_nodes)
+        return fail(MEL_ERR_INVALID_ARG, "n_scripted=%d for %d-node envs", st->n_scripted, env->n_nodes);
+    if (st->n_scripted > 0 && (!st->draw_scripted || !pool->scripted))
+        return fail(MEL_ERR_INVALID_ARG, "n_scripted=%d needs draw_scripted and pool->scripted", st->n_scripted);
     if (pool->n_episodes != B * K || pool->n_nodes != env->n_nodes || !pool->pos || !pool->one_hop || !pool->origin ||
         !pool->interested || (env->dynamic_graph && (!pool->moves || pool->max_moves < 1)))
         return fail(MEL_ERR_INVALID_ARG, "the ring pool must hold n_envs * ring = %d episodes", B * K);

@@ -8,7 +8,8 @@ loops (``melissa_amd.collect``) take their episodes from an :class:`EpisodeStrea
 * per env a RING of ``ring`` pool slots (episode j of env b lives in slot ``b * ring + j % ring``), the reset snapshot of
   every slot next to it;
 * ``mel_episode_refill`` (csrc/episode_stream.hpp) draws the next episodes of every env ON THE DEVICE with numpy's exact
-  algorithms (PCG64 ``Generator.integers`` / ``choice``; legacy MT19937 ``RandomState`` randint / uniform / choice /
+  algorithms (PCG64 ``Generator.integers`` / ``choice``, the scripted set's ``choice(N, k, replace=False)`` included -
+  World._sample_scripted_agents, core.py:197-215; legacy MT19937 ``RandomState`` randint / uniform / choice /
   the ``0.06 * uniform(-1, 1)`` movement offsets), copies the graph out of the packed dataset in HBM (the replacement of
   ``pickle.load`` per episode, core.py:450-452), and runs ``GraphEnv.reset`` + ``World.reset`` into the slot's snapshot;
 * the loop calls :meth:`before_step` / :meth:`after_step` once per iteration: every ``period`` iterations the refill is
@@ -18,7 +19,7 @@ loops (``melissa_amd.collect``) take their episodes from an :class:`EpisodeStrea
   kernels check that anyway (``MEL_ENV_ERR_EPISODE_UNDERRUN``).
 
 :class:`StaticSupply` is the old behaviour for explicitly given tables (tests) and for the modes the device sampler
-does not cover (evaluation schedule, scripted agents, a moving fixed graph): a fixed table; wrapping raises the same
+does not cover (evaluation schedule, a moving fixed graph, training mode with EVERY node scripted): a fixed table; wrapping raises the same
 error flag unless the table is periodic by construction (the evaluation schedule is, core.py:351-352).
 """
 from __future__ import annotations
@@ -34,8 +35,10 @@ from .episodes import pack_episodes
 
 
 def stream_supported(venv) -> bool:
+    """Training mode, scripted agents or not; not the evaluation schedule (a periodic table), not a fixed graph that moves
+    (its positions carry over), not ratio 1.0 (no agent is left for the policy: not playable)."""
     kw = venv._sampler_kw
-    return not (kw["is_testing"] or kw["scripted_agents_ratio"] > 0.0 or (venv.fixed_graph and venv.dynamic_graph))
+    return not (kw["is_testing"] or kw["scripted_agents_ratio"] >= 1.0 or (venv.fixed_graph and venv.dynamic_graph))
 
 
 class StaticSupply:
@@ -85,7 +88,8 @@ class EpisodeStream:
 
     def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
         if not stream_supported(venv):
-            raise ValueError("the device sampler covers training mode without scripted agents (and no moving fixed graph)")
+            raise ValueError("the device sampler covers training mode with fewer than all nodes scripted (and no moving "
+                             "fixed graph)")
         if ring < 3:
             raise ValueError("ring must be >= 3")
         self.venv, self.ring = venv, int(ring)
@@ -109,6 +113,9 @@ class EpisodeStream:
         self.draw_graph = torch.zeros(B * K, dtype=torch.int32, device=dev)
         self.work = torch.zeros(1 + 2 * B * K, dtype=torch.int32, device=dev)
         self.new_count = torch.zeros(B, dtype=torch.int32, device=dev)
+        # World._sample_scripted_agents: round() is Python's here (core.py:200); the device only draws that many
+        self.n_scripted = int(round(venv._sampler_kw["scripted_agents_ratio"] * n))
+        self.draw_scripted = torch.zeros(B * K, (n + 63) // 64, dtype=torch.int64, device=dev) if self.n_scripted else None
         # ---- the packed graph dataset in HBM
         self.graph_pos = torch.from_numpy(np.stack([g.pos for g in venv.graphs]).astype(np.float64)).to(dev)
         self.graph_hop = torch.from_numpy(np.stack([g.one_hop for g in venv.graphs]).astype(np.uint64).view(np.int64)).to(dev)
@@ -128,6 +135,8 @@ class EpisodeStream:
         s.pcg, s.pcg_half, s.produced = self.pcg.data_ptr(), self.pcg_half.data_ptr(), self.produced.data_ptr()
         s.draw_seed, s.draw_graph = self.draw_seed.data_ptr(), self.draw_graph.data_ptr()
         s.work, s.new_count = self.work.data_ptr(), self.new_count.data_ptr()
+        s.n_scripted = self.n_scripted
+        s.draw_scripted = self.draw_scripted.data_ptr() if self.n_scripted else None
         self.struct = s
         self.side = torch.cuda.Stream(device=dev)
         self._ev_main = torch.cuda.Event()

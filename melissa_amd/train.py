@@ -54,7 +54,8 @@ def policy_and_learner(name: str):
 
 def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4, batch_size=32, n_step=4,
           gamma=0.99, lr=1e-3, target_update_freq=500, eps=0.1, replay_rounds=64, seed=9, backend=None, log=print,
-          probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4):
+          probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
+          heuristic=None, scripted_agents_ratio=0.0):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -64,7 +65,10 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     have static shapes, replay.DGNLearner / replay.NDGNLearner).  None = on unless a probe is attached; with several ranks the collective stays
     eager between two graphs.  The capture takes two extra (real, untimed) updates first: ``warmup_updates`` in the result.
     ``prio_buffer`` / ``alpha`` / ``beta``: the reference's ``--prio-buffer --alpha --beta`` (common.py:52,64-65): sample from a
-    :class:`melissa_amd.replay.PrioritizedRoundReplay` (each rank owns its buffer; nothing more is exchanged)."""
+    :class:`melissa_amd.replay.PrioritizedRoundReplay` (each rank owns its buffer; nothing more is exchanged).
+    ``heuristic`` / ``scripted_agents_ratio``: the reference's ``--heuristic --scripted-agents-ratio`` (common.py:67,69; every
+    training script hands them to its training envs, l_dgn.py:137-146): that fraction of the nodes, drawn anew on every reset
+    by the device episode stream (core.py:197-217,395), runs the heuristic instead of the policy and is never recorded."""
     import torch
     from . import launch, parallel
     from .collect import RoundLoop
@@ -84,7 +88,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     from .env import cached_graph_pool
     graph_list = cached_graph_pool(n_nodes, graphs, 0) if graphs >= 4096 else synthetic_graph_pool(n_nodes, graphs, first_seed=0)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
-                             seed=1000 + rank * envs, construct_like_reference=False)
+                             seed=1000 + rank * envs, construct_like_reference=False, heuristic=heuristic,
+                             scripted_agents_ratio=scripted_agents_ratio)
     if prio_buffer:
         replay = PrioritizedRoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours, alpha=alpha, beta=beta)
     else:
@@ -126,7 +131,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                # the capture's warm-up updates are REAL optimizer steps taken before the timed loop (they advance the policy's
                # iteration counter and the replay sampler's generator): a run with capture on has taken `updates +
                # warmup_updates` steps, `seconds` covers `updates` of them
-               warmup_updates=warmup_updates)
+               warmup_updates=warmup_updates, heuristic=heuristic, scripted_agents_ratio=float(scripted_agents_ratio),
+               episode_supply=loop.supply.describe())
     # replicas must be identical after averaged-gradient steps
     same = parallel.all_reduce_max(checksum, device) == parallel.all_reduce_max(-checksum, device) * -1
     out["replicas_identical"] = bool(same)
@@ -154,6 +160,11 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prio-buffer", action="store_true", default=False, help="prioritized experience replay")
     ap.add_argument("--alpha", type=float, default=0.6, help="prioritization exponent")
     ap.add_argument("--beta", type=float, default=0.4, help="importance-weight exponent")
+    # the reference's names and defaults (common.py:67,69); the probabilistic heuristics are not offered
+    ap.add_argument("--heuristic", default=None, choices=["simple_broadcast", "broadcast_if_any_interested", "silent", "mpr"],
+                    help="heuristic the scripted agents run")
+    ap.add_argument("--scripted-agents-ratio", type=float, default=0.0,
+                    help="fraction of the nodes that are scripted agents, drawn anew for every episode")
     return ap
 
 
@@ -168,7 +179,8 @@ def main():
     train(model=a.model, n_nodes=a.nodes, envs=a.envs, updates=a.updates, rounds_per_update=a.rounds_per_update,
           batch_size=a.batch_size, backend=a.backend, graphs=a.graphs,
           capture_updates={"auto": None, "on": True, "off": False}[a.capture_updates],
-          prio_buffer=a.prio_buffer, alpha=a.alpha, beta=a.beta)
+          prio_buffer=a.prio_buffer, alpha=a.alpha, beta=a.beta, heuristic=a.heuristic,
+          scripted_agents_ratio=a.scripted_agents_ratio)
 
 
 if __name__ == "__main__":

@@ -33,7 +33,7 @@ def env_round_us(n, B, kw, rounds, graphs):
                              construct_like_reference=False, **kw)
     net = LDGNNetwork(5, 128, 2, 4, n, dueling_param=({"hidden_sizes": [128, 128]}, {"hidden_sizes": [128, 128]}),
                       device="cuda", backend="hip")
-    episodes = max(8, rounds // 5)          # host-drawn table (the device stream does not cover scripted agents)
+    episodes = max(8, rounds // 5)          # host-drawn table (one supply for all four settings: the device stream does not cover testing mode)
     loop = RoundLoop(venv, DQNPolicy(net), seed=1, eps=0.1, episodes=sample_episode_table(venv, episodes, 1))
     loop.run(10)
     torch.cuda.synchronize()
