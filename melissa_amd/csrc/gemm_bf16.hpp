@@ -87,18 +87,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_bf16_kernel(GemmBatch ba
     __shared__ float enc_s[MODE == GEMM_MODE_ENC ? ENC_MAX_K * 9 : 1];
     const float* enc = enc_s;
 
-    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];
-    pre[0] = 0;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-        act[i] = 0, rows[i] = 0;
-        if (i < batch.count) {
-            const GemmArgs& q = batch.p[i];
-            rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-            act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN) * (q.ksplit > 1 ? q.ksplit : 1);
-        }
-        pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
-    }
+    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];       // the work-item walk (gemm_walk.hpp)
+    walk_tables<BM, BN, true>(batch, act, pre, rows);
     const int total = pre[GEMM_MAX_GROUP];
     const int stride = gridDim.x;
 
@@ -111,38 +101,16 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_bf16_kernel(GemmBatch ba
     const int cch = tid & 7;              // this thread's chunk of the slice
     const int kc = cch * 8;               // first element of the chunk
 
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     auto setup = [&](BTileCtx<A_CHUNKS, W_CHUNKS>& c, int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {   // workgroups sharing an A row panel sit on one XCD (see gemm_f32.hpp)
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        // split-K (skinny long-K problems, see gemm_ring.hpp): work items of a row panel are ordered chunk-major; chunk ks
-        // covers K columns [k0, k0 + KT * GEMB_BK) and writes raw fp32 products to plane ks
-        const int S = g.ksplit > 1 ? g.ksplit : 1;
-        c.pi = pi, c.M = rows[pi], c.KT = g.K / GEMB_BK / S, c.ks = (wg / nbn) % S;
-        c.m0 = (wg / (nbn * S)) * BM, c.n0 = (wg % nbn) * BN;
+        // split-K (skinny long-K problems, see gemm_ring.hpp): chunk ks covers K columns [k0, k0 + KT * GEMB_BK) and writes
+        // raw fp32 products to plane ks
+        const WorkItem w = walk_item<BM, BN, true>(batch, t, act, pre, rows);
+        const GemmArgs& g = batch.p[w.pi];
+        c.pi = w.pi, c.M = w.M, c.KT = g.K / GEMB_BK / w.S, c.ks = w.ks;
+        c.m0 = w.m0, c.n0 = w.n0;
         const int k0 = c.ks * c.KT * GEMB_BK;
         const uint16_t* A16 = reinterpret_cast<const uint16_t*>(g.A) + k0;
-        const uint16_t* W16 = reinterpret_cast<const uint16_t*>(g.W) + k0;
-        const uint16_t* Wh16 = g.W_hi ? reinterpret_cast<const uint16_t*>(g.W_hi) + k0 : nullptr;
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) {
             const int row = min(c.m0 + crow + i * (T / 8), c.M - 1);      // clamped, never predicated
@@ -159,9 +127,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_bf16_kernel(GemmBatch ba
 #pragma unroll
         for (int i = 0; i < W_CHUNKS; ++i) {
             const int n = c.n0 + crow + i * (T / 8);
-            const uint16_t* base = (Wh16 && n >= g.split_n) ? Wh16 + (size_t)(n - g.split_n) * g.K
-                                                            : W16 + (size_t)n * g.K;
-            c.w_src[i] = reinterpret_cast<const u32x4*>(base + kc);
+            c.w_src[i] = reinterpret_cast<const u32x4*>(weight_row<uint16_t>(g, n, g.K) + k0 + kc);
         }
     };
 

@@ -72,8 +72,9 @@ struct GemmArgs {
     // kernel when the launch is large enough for it to win and the exact-fp32 kernel otherwise
     const float* Ws = nullptr;
     const float* Ws_hi = nullptr;
-    // split-K (specialised-wavefront kernel only): the K range is cut into `ksplit` equal chunks, chunk s writes its RAW
-    // partial products (no scale / bias / ReLU) to Y + s * part_stride; splitk_finish_kernel sums the planes in order
+    // split-K (gemm_f32_ring_kernel, gemm_bf16_kernel, gemm_split_big_kernel): the K range is cut into `ksplit` equal chunks,
+    // chunk s writes its RAW partial products (no scale / bias / ReLU) to Y + s * part_stride; splitk_finish_kernel sums the
+    // planes in order
     int ksplit = 0;
     long part_stride = 0;
 };
@@ -83,14 +84,28 @@ struct GemmArgs {
 constexpr int GEMM_MAX_GROUP = 4;
 struct GemmBatch {
     GemmArgs p[GEMM_MAX_GROUP];
-    int start[GEMM_MAX_GROUP + 1];   // first workgroup id of each problem (multiples of 8), total at [count]
+    // first workgroup id of each problem (multiples of 8), total at [count], for the rows the grid covers.  Only gemm_f32_tile
+    // reads it: the persistent kernels rebuild their prefix from the device-side row counts (walk_tables, gemm_walk.hpp), for
+    // them the host's value only sizes the grid
+    int start[GEMM_MAX_GROUP + 1];
     int count;
 };
+
+}  // namespace mel
+#include "gemm_walk.hpp"   // the work-item walk, over GemmArgs / GemmBatch
+namespace mel {
 
 constexpr int GEMM_BK = 32;
 constexpr int GEMM_LDS_STRIDE = GEMM_BK + 4;   // floats; 144-byte rows
 
 enum { GEMM_MODE_PLAIN = 0, GEMM_MODE_ENC = 1 };
+
+// Row n of the W operand in elements of T, `row_elems` per row: rows [0, split_n) come from W, the rest from W_hi
+template <class T>
+__device__ __forceinline__ const T* weight_row(const GemmArgs& g, int n, size_t row_elems) {
+    return (g.W_hi && n >= g.split_n) ? reinterpret_cast<const T*>(g.W_hi) + (size_t)(n - g.split_n) * row_elems
+                                      : reinterpret_cast<const T*>(g.W) + (size_t)n * row_elems;
+}
 
 // Per-thread staging coordinates of one 16-byte chunk (constant across K steps).
 struct AChunk {
@@ -214,19 +229,14 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmBatch& batch, const int 
     __shared__ __attribute__((aligned(16))) float lds[2 * BUF + (MODE == GEMM_MODE_ENC ? ENC_MAX_K * 9 : 0)];
     float* enc = lds + 2 * BUF;
 
-    // Tile order.  The row count may be ragged and device-side: only the first `active` workgroup ids
-    // have work (the dispatcher deals consecutive ids round-robin over the 8 XCDs, so they are spread
-    // evenly) and the rest exit at once.  Inside the active range ids are remapped (bijectively) so that
-    // the workgroups sharing an A row panel (same m tile, different n tile) sit on one XCD's L2.
+    // Tile order (gemm_walk.hpp).  The row count may be ragged and device-side: the grid covers g.M rows, the workgroups
+    // beyond the live tiles exit at once.
     const int nbn = g.N / BN;
-    const int M = g.M_dev ? min(*g.M_dev, g.M) : g.M;
-    const int active = ((M + BM - 1) / BM) * nbn;
+    const int M = gemm_rows(g);
+    const int active = gemm_items(M, g.N, BM, BN, 1);
     int wg = block - batch.start[pi];
     if (wg >= active) return;
-    {
-        const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-        wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-    }
+    wg = xcd_panel_order(wg, active);
     const int m0 = (wg / nbn) * BM;
     const int n0 = (wg % nbn) * BN;
 
@@ -263,9 +273,7 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmBatch& batch, const int 
 #pragma unroll
     for (int i = 0; i < W_CHUNKS; ++i) {
         const int n = n0 + crow + i * (T / 8);
-        const float* base = (g.W_hi && n >= g.split_n) ? g.W_hi + (size_t)(n - g.split_n) * g.K
-                                                        : g.W + (size_t)n * g.K;
-        w_src[i] = base + kc;
+        w_src[i] = weight_row<float>(g, n, g.K) + kc;
     }
 
     f32x16 acc[TM][TN];
@@ -476,19 +484,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_f32_persistent_kernel(Ge
     __shared__ __attribute__((aligned(16))) float lds[2 * BUF + (MODE == GEMM_MODE_ENC ? ENC_MAX_K * 9 : 0)];
     float* enc = lds + 2 * BUF;
 
-    // tile bookkeeping (wave-uniform): active tiles and padded prefix per problem
+    // tile bookkeeping (wave-uniform, gemm_walk.hpp): live rows, tiles and padded prefix per problem
     int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];
-    pre[0] = 0;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-        act[i] = 0, rows[i] = 0;
-        if (i < batch.count) {
-            const GemmArgs& q = batch.p[i];
-            rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-            act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN);
-        }
-        pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
-    }
+    walk_tables<BM, BN, false>(batch, act, pre, rows);
     const int total = pre[GEMM_MAX_GROUP];
     const int stride = gridDim.x;
 
@@ -500,32 +498,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_f32_persistent_kernel(Ge
     const int crow = tid >> 3;
     const int kc = (tid & 7) * 4;
 
-    // first valid tile at or after t (skips the per-problem padding)
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     auto setup = [&](TileCtx<A_CHUNKS, W_CHUNKS>& c, int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        c.pi = pi, c.M = rows[pi], c.KT = g.K / GEMM_BK;
-        c.m0 = (wg / nbn) * BM, c.n0 = (wg % nbn) * BN;
+        const WorkItem w = walk_item<BM, BN, false>(batch, t, act, pre, rows);
+        const GemmArgs& g = batch.p[w.pi];
+        c.pi = w.pi, c.M = w.M, c.KT = g.K / GEMM_BK;
+        c.m0 = w.m0, c.n0 = w.n0;
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) {
             const int row = min(c.m0 + crow + i * (T / 8), c.M - 1);
@@ -542,9 +520,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_f32_persistent_kernel(Ge
 #pragma unroll
         for (int i = 0; i < W_CHUNKS; ++i) {
             const int n = c.n0 + crow + i * (T / 8);
-            const float* base = (g.W_hi && n >= g.split_n) ? g.W_hi + (size_t)(n - g.split_n) * g.K
-                                                            : g.W + (size_t)n * g.K;
-            c.w_src[i] = base + kc;
+            c.w_src[i] = weight_row<float>(g, n, g.K) + kc;
         }
     };
 

@@ -196,10 +196,9 @@ static GemmPlan& choose(GemmPlan& p, GemmKernel kernel, int mode, const GemmArgs
     b = GemmBatch{};
     b.count = count;
     long items = 0;
-    for (int i = 0; i < count; ++i) {
-        const long ks = by_ksplit && gs[i].ksplit > 1 ? gs[i].ksplit : 1;
+    for (int i = 0; i < count; ++i) {       // the ids the kernels walk (gemm_walk.hpp), for the rows the grid covers
         b.p[i] = gs[i], b.start[i] = (int)items;
-        items += ((long)((gs[i].M + bm - 1) / bm) * (gs[i].N / bn) * ks + 7) & ~7L;
+        items += gemm_pad_items(gemm_items((long)gs[i].M, gs[i].N, bm, bn, by_ksplit ? gs[i].ksplit : 1));
     }
     b.start[count] = (int)items;
     p.grid = (int)(per_cu && items > 256L * per_cu ? 256L * per_cu : items);

@@ -91,52 +91,19 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
     // finished accumulator tile, handed from the consumers to the loaders
     __shared__ __attribute__((aligned(16))) float outbuf[BM * RING_OUT_STRIDE];
 
-    // tile bookkeeping (wave-uniform), identical for every wave of the workgroup
+    // tile bookkeeping (wave-uniform, gemm_walk.hpp), identical for every wave of the workgroup
     int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];
-    pre[0] = 0;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-        act[i] = 0, rows[i] = 0;
-        if (i < batch.count) {
-            const GemmArgs& q = batch.p[i];
-            rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-            act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN) * (q.ksplit > 1 ? q.ksplit : 1);
-        }
-        pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
-    }
+    walk_tables<BM, BN, true>(batch, act, pre, rows);
     const int total = pre[GEMM_MAX_GROUP];
     const int stride = gridDim.x;
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     struct Tile {
         int pi, m0, n0, M, KT, ks, k0;           // ks / k0: split-K chunk of this work item and its first K column
     };
     auto tile_of = [&](int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {   // workgroups sharing an A row panel sit on one XCD (see gemm_f32.hpp)
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        // split-K: the work items of one row panel are ordered chunk-major, so the nbn items that share an A chunk are
-        // neighbours
-        const int S = g.ksplit > 1 ? g.ksplit : 1;
-        const int ks = (wg / nbn) % S, KT = g.K / BK / S;
-        return Tile{pi, (wg / (nbn * S)) * BM, (wg % nbn) * BN, rows[pi], KT, ks, ks * KT * BK};
+        const WorkItem w = walk_item<BM, BN, true>(batch, t, act, pre, rows);
+        const int KT = batch.p[w.pi].K / BK / w.S;
+        return Tile{w.pi, w.m0, w.n0, w.M, KT, w.ks, w.ks * KT * BK};
     };
 
     const int first = next_valid(blockIdx.x);
@@ -168,9 +135,7 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
                     src[i] = g.A + (size_t)ar * g.lda + c.k0 + chunk * 4;
                 } else {
                     const int n = c.n0 + (row - BM);
-                    const float* base = (g.W_hi && n >= g.split_n) ? g.W_hi + (size_t)(n - g.split_n) * g.K
-                                                                    : g.W + (size_t)n * g.K;
-                    src[i] = base + c.k0 + chunk * 4;
+                    src[i] = weight_row<float>(g, n, g.K) + c.k0 + chunk * 4;
                 }
             }
         };

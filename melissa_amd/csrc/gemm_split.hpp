@@ -60,18 +60,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
     __shared__ float enc_s[MODE == GEMM_MODE_ENC ? ENC_MAX_K * 9 : 1];
     const float* enc = enc_s;
 
-    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];
-    pre[0] = 0;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-        act[i] = 0, rows[i] = 0;
-        if (i < batch.count) {
-            const GemmArgs& q = batch.p[i];
-            rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-            act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN);
-        }
-        pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
-    }
+    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];       // the work-item walk (gemm_walk.hpp)
+    walk_tables<BM, BN, false>(batch, act, pre, rows);
     const int total = pre[GEMM_MAX_GROUP];
     const int stride = gridDim.x;
 
@@ -85,31 +75,12 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
     const int wrow = tid >> 2;            // W staging: 4 threads per 64-byte plane slice, all 64 rows in one pass
     const int wch = tid & 3;
 
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     auto setup = [&](STileCtx<A_CHUNKS, W_CHUNKS>& c, int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        c.pi = pi, c.M = rows[pi], c.KT = g.K / GEMM_BK;
-        c.m0 = (wg / nbn) * BM, c.n0 = (wg % nbn) * BN;
+        const WorkItem w = walk_item<BM, BN, false>(batch, t, act, pre, rows);
+        const GemmArgs& g = batch.p[w.pi];
+        c.pi = w.pi, c.M = w.M, c.KT = g.K / GEMM_BK;
+        c.m0 = w.m0, c.n0 = w.n0;
 #pragma unroll
         for (int i = 0; i < A_CHUNKS; ++i) {
             const int row = min(c.m0 + crow + i * 32, c.M - 1);
@@ -126,9 +97,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
         {   // weights: [N][K / 16][3][16] bf16 planes (split_weights_kernel); W / W_hi point at row 0.  This thread's chunk
             // wch of plane p (k = 8 wch .. + 7 of the 32-k step) sits in 16-k step wch >> 1, half wch & 1
             const int n = c.n0 + wrow;
-            const uint16_t* base = (g.W_hi && n >= g.split_n)
-                                       ? reinterpret_cast<const uint16_t*>(g.W_hi) + (size_t)(n - g.split_n) * 3 * g.K
-                                       : reinterpret_cast<const uint16_t*>(g.W) + (size_t)n * 3 * g.K;
+            const uint16_t* base = weight_row<uint16_t>(g, n, (size_t)3 * g.K);
 #pragma unroll
             for (int p = 0; p < 3; ++p)
                 c.w_src[p] = reinterpret_cast<const u32x4*>(base + ((wch >> 1) * 3 + p) * 16 + (wch & 1) * 8);
@@ -138,13 +107,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
     int t = next_valid(blockIdx.x);
     if (t >= total) return;
     int nsteps = 0;                           // K steps of this workgroup's whole stream
-    for (int tt = t; tt < total; tt = next_valid(tt + stride)) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (tt >= pre[k]) pi = k;
-        nsteps += batch.p[pi].K / GEMM_BK;
-    }
+    for (int tt = t; tt < total; tt = next_valid(tt + stride)) nsteps += batch.p[walk_problem(tt, pre)].K / GEMM_BK;
     if constexpr (MODE == GEMM_MODE_ENC) {
         const GemmArgs& g = batch.p[0];
         float* e = enc_s;
@@ -276,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
 // ds_read_b128 group land on 16 distinct 16-byte slots), a stage 28 KB, two stages 56 KB: two workgroups per CU, so a
 // SIMD holds two waves of different workgroups and one's barrier / epilogue is the other's matrix time.  Same flat
 // stream of K steps across the workgroup's work items with the register prefetch two steps ahead; PLAIN mode only.
-// Split-K (GemmArgs::ksplit, as in gemm_bf16.hpp): work item = (tile, K chunk), raw products to plane ks.
+// Split-K (GemmArgs::ksplit, ordered as gemm_walk.hpp says): work item = (tile, K chunk), raw products to plane ks.
 #ifdef MEL_SPLIT_PROF
 __device__ unsigned long long g_split_prof[16];      // issue-time stamps inside a K step (tools/split_prof.py)
 #endif
@@ -295,18 +258,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
     constexpr int BUF = (BM + BN) * GEMS2_ROW;        // 16-byte chunks per LDS stage
     __shared__ u32x4 lds[2 * BUF];
 
-    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];
-    pre[0] = 0;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-        act[i] = 0, rows[i] = 0;
-        if (i < batch.count) {
-            const GemmArgs& q = batch.p[i];
-            rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-            act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN) * (q.ksplit > 1 ? q.ksplit : 1);
-        }
-        pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
-    }
+    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];       // the work-item walk (gemm_walk.hpp)
+    walk_tables<BM, BN, true>(batch, act, pre, rows);
     const int total = pre[GEMM_MAX_GROUP];
     const int stride = gridDim.x;
 
@@ -318,32 +271,12 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
     const int crow = tid >> 2;            // A staging: 4 threads per 64-byte fp32 row slice, 64 rows per pass, 2 passes
     const int kq = tid & 3;               // this thread's 4 consecutive k of the step
 
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     auto setup = [&](S2TileCtx& c, int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        const int S = g.ksplit > 1 ? g.ksplit : 1;
-        c.pi = pi, c.M = rows[pi], c.KT = g.K / GEMS2_BK / S, c.ks = (wg / nbn) % S;
-        c.m0 = (wg / (nbn * S)) * BM, c.n0 = (wg % nbn) * BN;
+        const WorkItem w = walk_item<BM, BN, true>(batch, t, act, pre, rows);
+        const GemmArgs& g = batch.p[w.pi];
+        c.pi = w.pi, c.M = w.M, c.KT = g.K / GEMS2_BK / w.S, c.ks = w.ks;
+        c.m0 = w.m0, c.n0 = w.n0;
         const int step0 = c.ks * c.KT;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -355,9 +288,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
         for (int i = 0; i < 3; ++i) {       // [N][K / 16][3][16] planes: 6 chunks per row and step, 768 per tile and step
             const int ch = tid + i * 256, wrow = ch / 6, wch = ch - wrow * 6;
             const int n = c.n0 + wrow;
-            const uint16_t* base = (g.W_hi && n >= g.split_n)
-                                       ? reinterpret_cast<const uint16_t*>(g.W_hi) + (size_t)(n - g.split_n) * 3 * g.K
-                                       : reinterpret_cast<const uint16_t*>(g.W) + (size_t)n * 3 * g.K;
+            const uint16_t* base = weight_row<uint16_t>(g, n, (size_t)3 * g.K);
             c.w_src[i] = reinterpret_cast<const u32x4*>(base + (size_t)step0 * 48 + wch * 8);
         }
     };
@@ -366,11 +297,8 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
     if (t >= total) return;
     int nsteps = 0;                           // K steps of this workgroup's whole stream
     for (int tt = t; tt < total; tt = next_valid(tt + stride)) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (tt >= pre[k]) pi = k;
-        nsteps += batch.p[pi].K / GEMS2_BK / (batch.p[pi].ksplit > 1 ? batch.p[pi].ksplit : 1);
+        const GemmArgs& g = batch.p[walk_problem(tt, pre)];
+        nsteps += g.K / GEMS2_BK / (g.ksplit > 1 ? g.ksplit : 1);
     }
 
     // LDS addressing: 8-byte units for the A pieces (row * 14 + plane * 4 + kq), 16-byte chunks elsewhere
@@ -628,22 +556,20 @@ __global__ __launch_bounds__(768, 3) void gemm_planes_kernel(GemmBatch batch) {
     float* xpose = reinterpret_cast<float*>(lds + GEMP_STAGES * BUF);
     float* bias_s = xpose + 4 * XP;
 
-    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP], boff[GEMM_MAX_GROUP];
-    pre[0] = 0;
+    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];       // the work-item walk (gemm_walk.hpp)
+    walk_tables<BM, BN, false>(batch, act, pre, rows);
+    int boff[GEMM_MAX_GROUP];                 // the biases of problem i are staged at bias_s + boff[i]
     {
         int o = 0;
 #pragma unroll
         for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-            act[i] = 0, rows[i] = 0, boff[i] = o;
+            boff[i] = o;
             if (i < batch.count) {
                 const GemmArgs& q = batch.p[i];
-                rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-                act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN);
                 for (int n = threadIdx.x; n < q.N; n += 768)
                     bias_s[o + n] = (q.bias_hi && n >= q.split_n) ? q.bias_hi[n - q.split_n] : (q.bias ? q.bias[n] : 0.f);
                 o += q.N;
             }
-            pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
         }
     }
     const int total = pre[GEMM_MAX_GROUP];
@@ -651,36 +577,13 @@ __global__ __launch_bounds__(768, 3) void gemm_planes_kernel(GemmBatch batch) {
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // 0-7 MFMA waves, 8-11 loader waves
 
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     struct Meta {
         int m0, n0, M, pi, KT;
     };
     auto meta_of = [&](int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        Meta m;
-        m.pi = pi, m.M = rows[pi], m.KT = g.K / GEMS2_BK;
-        m.m0 = (wg / nbn) * BM, m.n0 = (wg % nbn) * BN;
-        return m;
+        const WorkItem w = walk_item<BM, BN, false>(batch, t, act, pre, rows);
+        return Meta{w.m0, w.n0, w.M, w.pi, batch.p[w.pi].K / GEMS2_BK};
     };
 
     const int t0 = next_valid(blockIdx.x);
@@ -920,22 +823,20 @@ __global__ __launch_bounds__(768, 3) void gemm_bf16_wide_kernel(GemmBatch batch)
     __shared__ u32x4 lds[GEMP_STAGES * BUF + GEMP_BIAS_FLOATS / 4];
     float* bias_s = reinterpret_cast<float*>(lds + GEMP_STAGES * BUF);
 
-    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP], boff[GEMM_MAX_GROUP];
-    pre[0] = 0;
+    int act[GEMM_MAX_GROUP], pre[GEMM_MAX_GROUP + 1], rows[GEMM_MAX_GROUP];       // the work-item walk (gemm_walk.hpp)
+    walk_tables<BM, BN, false>(batch, act, pre, rows);
+    int boff[GEMM_MAX_GROUP];                 // the biases of problem i are staged at bias_s + boff[i]
     {
         int o = 0;
 #pragma unroll
         for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
-            act[i] = 0, rows[i] = 0, boff[i] = o;
+            boff[i] = o;
             if (i < batch.count) {
                 const GemmArgs& q = batch.p[i];
-                rows[i] = q.M_dev ? min(*q.M_dev, q.M) : q.M;
-                act[i] = ((rows[i] + BM - 1) / BM) * (q.N / BN);
                 for (int n = threadIdx.x; n < q.N; n += 768)
                     bias_s[o + n] = (q.bias_hi && n >= q.split_n) ? q.bias_hi[n - q.split_n] : (q.bias ? q.bias[n] : 0.f);
                 o += q.N;
             }
-            pre[i + 1] = pre[i] + ((act[i] + 7) & ~7);
         }
     }
     const int total = pre[GEMM_MAX_GROUP];
@@ -943,36 +844,13 @@ __global__ __launch_bounds__(768, 3) void gemm_bf16_wide_kernel(GemmBatch batch)
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // 0-7 MFMA waves, 8-11 loader waves
 
-    auto next_valid = [&](int t) {
-        for (; t < total; t += stride) {
-            int pi = 0;
-#pragma unroll
-            for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-                if (t >= pre[k]) pi = k;
-            if (t - pre[pi] < act[pi]) return t;
-        }
-        return total;
-    };
+    auto next_valid = [&](int t) { return walk_next_valid(t, stride, act, pre); };
     struct Meta {
         int m0, n0, M, pi, KT;
     };
     auto meta_of = [&](int t) {
-        int pi = 0;
-#pragma unroll
-        for (int k = 1; k < GEMM_MAX_GROUP; ++k)
-            if (t >= pre[k]) pi = k;
-        const GemmArgs& g = batch.p[pi];
-        const int nbn = g.N / BN;
-        int wg = t - pre[pi];
-        {
-            const int active = act[pi];
-            const int q = active >> 3, r8 = active & 7, xcd = wg & 7, local = wg >> 3;
-            wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + local;
-        }
-        Meta m;
-        m.pi = pi, m.M = rows[pi], m.KT = g.K / GEMW_BK;
-        m.m0 = (wg / nbn) * BM, m.n0 = (wg % nbn) * BN;
-        return m;
+        const WorkItem w = walk_item<BM, BN, false>(batch, t, act, pre, rows);
+        return Meta{w.m0, w.n0, w.M, w.pi, batch.p[w.pi].K / GEMW_BK};
     };
 
     const int t0 = next_valid(blockIdx.x);
