@@ -188,10 +188,14 @@ mel_status mel_ldgn_forward(const mel_weights* w, const float* obs, int64_t bs, 
  * select (optional): also write each row's action (see mel_select).
  * Each row equals mel_ldgn_forward on (obs_matrix, agent) within fp32 rounding. */
 /* Optional fused action selection for mel_ldgn_forward_agents: argmax of each logits row (+ eps-greedy with
- * the same counter-based stream as mel_select_action_rows) written by the kernel that produces the logits. */
+ * the same counter-based stream as mel_select_action_rows) written by the kernel that produces the logits.
+ * The exploration rate is `eps`, a host value fixed when the launch is issued (and frozen into a captured HIP graph), unless
+ * `eps_dev` is set: then every selection reads the rate from that device float when it RUNS (e.g. the value
+ * mel_exploration_schedule wrote just before on the same stream) and `eps` is ignored - a replayed graph follows a schedule
+ * without being recaptured.  The stream of draws is the same either way: eps_dev -> x selects what eps = x selects. */
 typedef struct mel_select {
     int32_t*        act;       /* device int32 [rows_cap]                                          */
-    float           eps;
+    float           eps;       /* exploration rate when eps_dev is NULL                            */
     uint32_t        seed;
     const uint32_t* step_dev;  /* optional device counter added to the stream position             */
     /* per-env logits (HL-DGN, mel_hldgn_forward_envs_select): every agent i in live[b] takes its action from row b,
@@ -200,6 +204,7 @@ typedef struct mel_select {
     const uint64_t* live;      /* node sets [bs]; NULL: one action per logits row                   */
     int32_t         n_nodes;
     int32_t         reserved;
+    const float*    eps_dev;   /* optional device float [1]: the exploration rate, read at run time */
 } mel_select;
 
 size_t mel_workspace_bytes_agents(const mel_weights* w, int64_t bs, int32_t n_nodes, int64_t rows_cap);
@@ -375,6 +380,24 @@ mel_status mel_select_action_rows(const float* logits, const int32_t* logit_row,
 mel_status mel_select_action_envs(const float* logits, const uint64_t* live, int64_t bs, int32_t n_nodes,
                                   int32_t n_actions, float eps, uint32_t seed, const uint32_t* step_dev,
                                   int32_t* act, void* stream);
+
+/* The exploration schedule of the reference's trainers (train_fn, l_dgn.py:225-234) evaluated ON THE DEVICE from the env
+ * batch's own decision counters, so that a captured round follows it with no host involvement:
+ *   env_step = scale * sum_b decisions[b * stride]                    (64-bit integer sum: deterministic)
+ *   horizon  = exploration_fraction * total_steps                     (total_steps = --epoch * --step-per-epoch)
+ *   eps      = max(eps_train * exp(env_step * ln(eps_final) / horizon), eps_final)      in double, rounded once to float
+ * decisions: device int32, n_envs elements `stride` elements apart (the round loop passes &scalars[0][MEL_S_DECISIONS] with
+ * stride MEL_ENV_SCALARS); scale: the world size (every rank collects as many decisions again).  Outputs (device):
+ * eps_out float [1] (what mel_select.eps_dev points at), env_step_out uint64 [1] (optional), and - with trace_cap > 0 -
+ * trace_env_step uint64 [trace_cap] / trace_eps float [trace_cap] at index *round_dev % trace_cap (round_dev: optional device
+ * counter, e.g. the one mel_env_round advances; NULL = index 0).  One launch of one workgroup, no host reads, no allocation:
+ * capturable (with a stage timer attached it is booked under MEL_STAGE_SELECT: that stage then holds one launch more per
+ * round than in a run without a schedule).  MEL_ERR_INVALID_ARG: horizon <= 0, eps_final <= 0, eps_final > eps_train (or not finite), a null decisions /
+ * eps_out, n_envs < 1, stride < 1, trace_cap > 0 without both trace arrays. */
+mel_status mel_exploration_schedule(const int32_t* decisions, int32_t stride, int32_t n_envs, uint32_t scale,
+                                    double eps_train, double eps_final, double exploration_fraction, double total_steps,
+                                    const uint32_t* round_dev, float* eps_out, uint64_t* env_step_out, int32_t trace_cap,
+                                    uint64_t* trace_env_step, float* trace_eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Environment half.  State of B independent envs lives in caller-owned device memory laid out as

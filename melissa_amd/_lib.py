@@ -40,7 +40,7 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
-           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets")
+           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -76,7 +76,7 @@ class MelWeights(C.Structure):
 
 class MelSelect(C.Structure):
     _fields_ = [("act", C.c_void_p), ("eps", C.c_float), ("seed", C.c_uint32), ("step_dev", C.c_void_p),
-                ("live", C.c_void_p), ("n_nodes", C.c_int32), ("reserved", C.c_int32)]
+                ("live", C.c_void_p), ("n_nodes", C.c_int32), ("reserved", C.c_int32), ("eps_dev", C.c_void_p)]
 
 
 class MelRoundReplay(C.Structure):
@@ -233,6 +233,9 @@ def load(build_if_missing: bool = True):
     lib.mel_ldgn_forward_agents.argtypes = [W, vp, i64, i32, i32, vp, i64, vp, vp, C.POINTER(MelSelect), vp, sz, vp]
     lib.mel_select_action_rows.restype = i32
     lib.mel_select_action_rows.argtypes = [vp, vp, i64, vp, i32, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp]
+    lib.mel_exploration_schedule.restype = i32
+    lib.mel_exploration_schedule.argtypes = [vp, i32, i32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp,
+                                             i32, vp, vp, vp]
     lib.mel_select_action.restype = i32
     lib.mel_select_action.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp, vp, vp, vp]
     lib.mel_env_state_bytes.restype = sz

@@ -15,6 +15,7 @@ of the reference's per-reset pickle.load + RNG draws).  Replay-buffer routing
 from __future__ import annotations
 
 import dataclasses
+import math
 
 import numpy as np
 import torch
@@ -36,6 +37,38 @@ def sample_episode_table(venv: HipGraphVectorEnv, episodes_per_env: int, seed: i
             episodes.append(sampler.sample())
     packed = pack_episodes(episodes, venv.graphs, venv.n, venv.max_moves, venv.dynamic_graph)
     return packed, table
+
+
+@dataclasses.dataclass
+class EpsSchedule:
+    """The exploration schedule of the reference's trainers (``train_fn``, l_dgn.py:225-234): eps decays from ``eps_train`` to
+    ``eps_final`` over ``exploration_fraction`` of the ``epoch * step_per_epoch`` env steps of a run, as a function of the env
+    steps collected so far.  Given to :class:`RoundLoop`, the device evaluates it before every round from the envs' own
+    decision counters (``mel_exploration_schedule``); ``scale``: env steps per decision of THIS loop (the world size when every
+    rank collects as much again), ``trace``: keep the (env_step, eps) of the last ``trace`` rounds in a device ring."""
+    eps_train: float = 1.0
+    eps_final: float = 0.05
+    exploration_fraction: float = 0.6
+    epoch: int = 10
+    step_per_epoch: int = 100000
+    scale: int = 1
+    trace: int = 0
+
+    @property
+    def total_steps(self) -> int:
+        return self.epoch * self.step_per_epoch
+
+    def eps(self, env_step: int) -> float:
+        return exploration_eps(env_step, self.eps_train, self.eps_final, self.exploration_fraction, self.epoch,
+                               self.step_per_epoch)
+
+
+def exploration_eps(env_step: int, eps_train: float = 1.0, eps_final: float = 0.05, exploration_fraction: float = 0.6,
+                    epoch: int = 10, step_per_epoch: int = 100000) -> float:
+    """eps after ``env_step`` collected env steps, in the reference's own arithmetic (l_dgn.py:229-233) - the host-side
+    statement of what ``mel_exploration_schedule`` computes as ``eps_train * exp(env_step * ln(eps_final) / horizon)``."""
+    decay_factor = 1.0 - math.pow(math.e, math.log(eps_final) / (exploration_fraction * epoch * step_per_epoch))
+    return max(eps_train * (1.0 - decay_factor) ** env_step, eps_final)
 
 
 def _counters_of(scalars: torch.Tensor, iterations: int) -> dict:
@@ -112,10 +145,13 @@ class RoundLoop:
     def __init__(self, venv: HipGraphVectorEnv, policy, episodes_per_env: int = 8, seed: int = 0,
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
                  stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: bool | None = None,
-                 ring: int = 16, discard: int = 0, graph_rounds: int = 4):
+                 ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
-        ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes."""
+        ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes.
+        ``eps_schedule`` (:class:`EpsSchedule`): every round starts with one small launch that computes eps from the envs'
+        decision counters and the selection reads that device value instead of ``eps`` - eager rounds and replayed graphs
+        alike, nothing is recaptured when eps changes."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
         self.use_graph, self.graph = use_graph, None
         # run(): whole groups of `graph_rounds` rounds are replayed from ONE HIP graph - a graph launch costs the device ~8 us
@@ -154,6 +190,14 @@ class RoundLoop:
         self._select.seed, self._select.step_dev = seed & 0xFFFFFFFF, self.rounds.data_ptr()
         if self.per_env_logits:                    # every agent of live[b] draws from env b's logits row
             self._select.live, self._select.n_nodes = self.live.data_ptr(), venv.n
+        self.eps_schedule = eps_schedule
+        if eps_schedule is not None:
+            cap = max(0, int(eps_schedule.trace))
+            self._eps_dev = torch.full((1,), float(eps_schedule.eps_train), dtype=torch.float32, device=dev)
+            self._env_step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._trace_env_step = torch.zeros(cap, dtype=torch.int64, device=dev)
+            self._trace_eps = torch.zeros(cap, dtype=torch.float32, device=dev)
+            self._select.eps_dev = self._eps_dev.data_ptr()
         self._obs_matrix = venv.obs_matrix()
         # own forward scratch: several loops may share one network on different streams
         self.workspace = torch.empty(policy.model.agents_workspace_bytes(venv.env_num, self.rows_cap),
@@ -175,9 +219,9 @@ class RoundLoop:
 
     def _launch(self):
         """The fixed launch sequence of one round (no host reads, no allocation: capturable)."""
-        lib = _lib.load()
         net = self.policy.model
-        dev = self.venv.device
+        if self.eps_schedule is not None:
+            self._launch_schedule()
         if self.per_env_logits:
             # forward + per-(env, agent) argmax / eps-greedy in the launch that writes the logits (same stream of draws as
             # mel_select_action_envs)
@@ -195,6 +239,31 @@ class RoundLoop:
         self._bind_plan()
         self.venv.round_device(self.pool, self.act, self.offsets, self.live, self.table, round_counter=self.rounds,
                                replay=self.replay)
+
+    def _launch_schedule(self):
+        """eps of the round about to be played, from the decisions collected before it (read by the selection through
+        ``mel_select.eps_dev``)."""
+        sch, cap = self.eps_schedule, self._trace_eps.numel()
+        _lib.check(_lib.load().mel_exploration_schedule(
+            self.venv.scalars().data_ptr() + 4 * _lib.S_DECISIONS, _lib.ENV_SCALARS, self.venv.env_num, int(sch.scale),
+            float(sch.eps_train), float(sch.eps_final), float(sch.exploration_fraction), float(sch.total_steps),
+            self.rounds.data_ptr(), self._eps_dev.data_ptr(), self._env_step_dev.data_ptr(), cap,
+            self._trace_env_step.data_ptr() if cap else None, self._trace_eps.data_ptr() if cap else None,
+            _lib.current_stream_ptr(self.venv.device)), "mel_exploration_schedule")
+
+    def eps_now(self):
+        """(env_step, eps) of the last scheduled round, read from the device (synchronises); without a schedule
+        (None, the host eps)."""
+        if self.eps_schedule is None:
+            return None, float(self.eps)
+        return int(self._env_step_dev.item()), float(self._eps_dev.item())
+
+    def eps_trace(self):
+        """The schedule's trace ring as (env_step int64 [trace], eps float32 [trace]): slot ``r % trace`` holds round r's
+        values (synchronises).  Needs a schedule."""
+        if self.eps_schedule is None:
+            raise RuntimeError("eps_trace(): this RoundLoop was built without eps_schedule")
+        return self._trace_env_step.cpu().numpy(), self._trace_eps.cpu().numpy()
 
     def step(self):
         if self.stream is not None:

@@ -2,6 +2,8 @@
 // field), fp32-MFMA row GEMMs (gemm_f32.hpp), GATv2 edge-softmax/aggregate, segmented pool, dueling
 // tail, DQN action selection.  Reference semantics: networks/common.py:6-64, l_dgn.py:92-151,
 // hl_dgn.py:82-119 and SURVEY.md Appendix A for the third-party operators.
+#include <cmath>
+
 #include "common.hpp"
 #include "gemm_launch.hpp"
 #include "plan.hpp"
@@ -737,7 +739,7 @@ size_t mel_abi_sizeof(int32_t which) {
         default: return 0;
     }
 }
-const char* mel_version(void) { return "melissa_hip 0.5 (gfx950)"; }
+const char* mel_version(void) { return "melissa_hip 0.6 (gfx950)"; }
 
 size_t mel_prepared_weights_bytes(const mel_weights* w) {
     if (!w || w->precision < MEL_PREC_F32 || w->precision > MEL_PREC_F32_AUTO) return 0;
@@ -1168,6 +1170,29 @@ mel_status mel_select_action(const float* logits, const uint8_t* mask, int64_t b
     MEL_LAUNCH(select_action_kernel, dim3((bs + 255) / 256), dim3(256), 0, s, logits, mask, (long)bs, na, eps,
                        rand_u, rand_q, static_cast<const float*>(scratch), act);
     return check_launch("select_action");
+}
+
+mel_status mel_exploration_schedule(const int32_t* decisions, int32_t stride, int32_t n_envs, uint32_t scale,
+                                    double eps_train, double eps_final, double exploration_fraction, double total_steps,
+                                    const uint32_t* round_dev, float* eps_out, uint64_t* env_step_out, int32_t trace_cap,
+                                    uint64_t* trace_env_step, float* trace_eps, void* stream) {
+    if (!decisions || !eps_out || n_envs < 1 || stride < 1) return fail(MEL_ERR_INVALID_ARG, "bad exploration_schedule arguments");
+    if (trace_cap < 0 || (trace_cap > 0 && (!trace_env_step || !trace_eps)))
+        return fail(MEL_ERR_INVALID_ARG, "exploration_schedule: a trace ring needs both arrays");
+    const double horizon = exploration_fraction * total_steps;
+    // (negated comparisons: a NaN fails them too)
+    if (!(horizon > 0.0) || !std::isfinite(horizon)) return fail(MEL_ERR_INVALID_ARG, "exploration_schedule: horizon %g <= 0", horizon);
+    if (!(eps_final > 0.0)) return fail(MEL_ERR_INVALID_ARG, "exploration_schedule: eps_final %g <= 0", eps_final);
+    if (!(eps_final <= eps_train) || !std::isfinite(eps_train))
+        return fail(MEL_ERR_INVALID_ARG, "exploration_schedule: eps_final %g > eps_train %g", eps_final, eps_train);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    clear_stale_error();
+    StageScope t(MEL_STAGE_SELECT, s);
+    MEL_LAUNCH(exploration_schedule_kernel, dim3(1), dim3(256), 0, s, decisions, (int)stride, (int)n_envs, scale, eps_train,
+                       eps_final, std::log(eps_final) / horizon, round_dev, eps_out,
+                       reinterpret_cast<unsigned long long*>(env_step_out), (int)trace_cap,
+                       reinterpret_cast<unsigned long long*>(trace_env_step), trace_eps);
+    return check_launch("exploration_schedule");
 }
 
 mel_status mel_select_action_envs(const float* logits, const uint64_t* live, int64_t bs, int32_t n, int32_t na,

@@ -18,6 +18,9 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {     // lowbias32 integer
 }
 __device__ __forceinline__ float u01(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
 
+// the exploration rate of a fused selection: the host value, or - eps_dev set - the device float a schedule launch wrote
+// earlier on the stream (one wave-uniform load; the draws that follow are the same function of the rate either way)
+__device__ __forceinline__ float sel_eps(const mel_select& sel) { return sel.eps_dev ? *sel.eps_dev : sel.eps; }
 
 // fused DQN action selection of row b from its dueling-combined values q[a] - mean + v
 __device__ __forceinline__ void select_fused(const float (&q)[8], float mean, float v, int na, const mel_select& sel, int b) {
@@ -26,10 +29,11 @@ __device__ __forceinline__ void select_fused(const float (&q)[8], float mean, fl
 #pragma unroll
     for (int a = 0; a < 8; ++a)
         if (a < na && q[a] - mean + v > bv) bv = q[a] - mean + v, best = a;
-    if (sel.eps > 0.f) {
+    const float eps = sel_eps(sel);
+    if (eps > 0.f) {
         const uint32_t step = sel.step_dev ? *sel.step_dev : 0u;
         const uint32_t base = mix32(sel.seed ^ mix32(step * 0x9e3779b9U + (uint32_t)b));
-        if (u01(base) < sel.eps) {
+        if (u01(base) < eps) {
             best = 0, bv = -1.f;
             for (int a = 0; a < na; ++a) {
                 const float u = u01(mix32(base + 0x85ebca6bU * (uint32_t)(a + 1)));
@@ -55,10 +59,11 @@ __device__ __forceinline__ void select_env_agent(const float (&q)[8], float mean
 #pragma unroll
     for (int a = 0; a < 8; ++a)
         if (a < na && q[a] - mean + v > bv) bv = q[a] - mean + v, best = a;
-    if (sel.eps > 0.f) {
+    const float eps = sel_eps(sel);
+    if (eps > 0.f) {
         const uint32_t step = sel.step_dev ? *sel.step_dev : 0u;
         const uint32_t base = mix32(sel.seed ^ mix32(step * 0x9e3779b9U + env_agent_key(b, sel.n_nodes, i)));
-        if (u01(base) < sel.eps) {
+        if (u01(base) < eps) {
             best = 0, bv = -1.f;
             for (int a = 0; a < na; ++a) {
                 const float u = u01(mix32(base + 0x85ebca6bU * (uint32_t)(a + 1)));
@@ -67,6 +72,40 @@ __device__ __forceinline__ void select_env_agent(const float (&q)[8], float mean
         }
     }
     sel.act[(size_t)b * sel.n_nodes + i] = best;
+}
+
+// ------------------------------------------------------------------------------------------------
+// exploration schedule (train_fn, l_dgn.py:225-234) from the device's decision counters; ONE workgroup of 256 lanes:
+// 64-bit integer partial sums per lane -> butterfly per wave -> LDS -> wave 0, so the sum is the same whatever n_envs is.
+// l_dgn.py:229-233 writes eps_train * (1 - (1 - e^k))^env_step with k = ln(eps_final) / horizon: algebraically
+// eps_train * exp(env_step * k), evaluated here in double in that form.  The reference's 1 - (1 - a) detour is exact for
+// a = e^k in [0.5, 1] (every horizon >= 5 steps), and its pow(a, env_step) carries a's rounding env_step times: a relative
+// 1.1e-16 * env_step <= 1e-9 before the clamp at eps_final ends the decay, for any run length the CLI allows - far below
+// the float ulp (6e-8 at 1.0) the result is rounded to.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void exploration_schedule_kernel(const int32_t* __restrict__ decisions, int stride, int n_envs,
+                                                                   uint32_t scale, double eps_train, double eps_final, double k,
+                                                                   const uint32_t* __restrict__ round_dev,
+                                                                   float* __restrict__ eps_out,
+                                                                   unsigned long long* __restrict__ env_step_out, int trace_cap,
+                                                                   unsigned long long* __restrict__ trace_env_step,
+                                                                   float* __restrict__ trace_eps) {
+    __shared__ long long part[4];
+    long long s = 0;
+    for (int b = threadIdx.x; b < n_envs; b += 256) s += (long long)decisions[(size_t)b * stride];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane_id() == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const unsigned long long env_step = (unsigned long long)(part[0] + part[1] + part[2] + part[3]) * scale;
+    const float eps = (float)fmax(eps_train * exp((double)env_step * k), eps_final);
+    *eps_out = eps;
+    if (env_step_out) *env_step_out = env_step;
+    if (trace_cap > 0) {
+        const uint32_t slot = (round_dev ? *round_dev : 0u) % (uint32_t)trace_cap;
+        trace_env_step[slot] = env_step;
+        trace_eps[slot] = eps;
+    }
 }
 
 // last Linear of Q and V + dueling combine + selection for ONE row held by one wave; hq / hv: the row's hidden

@@ -11,7 +11,9 @@ so all replicas stay bit-identical.  Target-network sync, eps schedule and count
 from __future__ import annotations
 
 import argparse
+import datetime
 import json
+import os
 import time
 
 # torch and the package's GPU-facing modules are imported inside the functions that need them: ``python -m melissa_amd.train
@@ -52,10 +54,152 @@ def policy_and_learner(name: str):
     return DQNPolicy, DQNLearner, False
 
 
+def default_model_name() -> str:
+    """common.py:54: the reference names a run after the time it starts."""
+    return datetime.datetime.now().strftime("%y%m%d-%H%M%S")
+
+
+def _param_checksum(net) -> float:
+    import torch
+    return float(torch.cat([p.detach().flatten() for p in net.parameters()]).double().sum())
+
+
+def _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scripted_agents_ratio) -> dict:
+    """``test_num`` episodes of the evaluation schedule at ``eps_test`` with the training policy's network (``test_fn`` +
+    ``episode_per_test``, l_dgn.py:240-253), on an env built as :func:`melissa_amd.watch.watch` builds it.  ONE env, like the
+    reference's ``test_envs``: every env of a batch walks the same list of test seeds, more envs would repeat episodes.  The
+    env is built anew for every evaluation, so each one plays the same ``test_num`` episodes from the top of that list.
+    -> rew / len / the ``logger_stats`` means over those episodes."""
+    import numpy as np
+    from . import _lib
+    from .collect import Collector
+    from .env import HipGraphVectorEnv, synthetic_graph_pool
+    venv = HipGraphVectorEnv(1, n_nodes, graph_pool=synthetic_graph_pool(n_nodes, 16, first_seed=0), dynamic_graph=True,
+                             device=device, max_moves=64, seed=seed, construct_like_reference=False, is_testing=True,
+                             num_test_episodes=test_num, scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic)
+    col = Collector(policy, venv, episodes_per_env=test_num + 2, seed=seed, eps=eps_test, chunk=4, use_graph=False)
+    was_training = policy.model.training
+    policy.model.eval()                                        # (as watch() and [3P] test_episode do; back to train mode after)
+    try:
+        res = col.collect(n_episode=test_num)
+    finally:
+        policy.model.train(was_training)
+    # (the last chunk of rounds may finish an episode more than asked for: the first test_num count)
+    out = dict(rew=float(np.mean(res.returns[:test_num])), len=float(np.mean(res.lens[:test_num])), episodes=int(test_num))
+    out.update({k: float(np.mean(res.episode_info[k][:test_num])) for k in _lib.LOGGER_KEYS})
+    return out
+
+
+def _agreed_decisions(loop, world, device) -> int:
+    """The decision count every rank uses for the run's env steps: the smallest rank's (a host read: synchronises)."""
+    from . import parallel
+    own = loop.counters()["decisions"]
+    return own if world == 1 else -int(parallel.all_reduce_max(-float(own), device))
+
+
+class _StaleDecisionCount:
+    """The agreed decision count as it stood one update iteration ago: ``push`` enqueues a snapshot of the device counters
+    (``RoundLoop.snapshot_counters``), their sum and its copy into pinned host memory, and hands back the count of the PREVIOUS
+    push, whose copy has long been done - one host read per iteration that waits for nothing still queued, so the launch queue
+    never drains.  With several ranks the smallest rank's count is what every rank gets (a device all-reduce in the same queue),
+    the same number :func:`_agreed_decisions` gives: compared with a target derived from that number too, every rank ends an
+    epoch at the same iteration - it must, because the gradient all-reduce pairs the ranks' updates one to one."""
+
+    def __init__(self, loop, world):
+        import torch
+        self.loop, self.world = loop, world
+        self.host = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self.done = [torch.cuda.Event(), torch.cuda.Event()]
+        self.pushed = 0
+
+    def push(self):
+        import torch
+        import torch.distributed as dist
+        from . import _lib
+        scalars, _ = self.loop.snapshot_counters()
+        count = scalars[:, _lib.S_DECISIONS].sum(dtype=torch.int64).reshape(1)
+        if self.world > 1:
+            if dist.get_backend() == "gloo":                   # (host tensors: the rehearsal backend synchronises)
+                h = count.cpu()
+                dist.all_reduce(h, op=dist.ReduceOp.MIN)
+                count = h.to(count.device)
+            else:
+                dist.all_reduce(count, op=dist.ReduceOp.MIN)
+        k = self.pushed & 1
+        self.pushed += 1
+        previous = None
+        if self.pushed > 1:
+            self.done[k ^ 1].synchronize()
+            previous = int(self.host[k ^ 1][0])
+        self.host[k].copy_(count, non_blocking=True)
+        self.done[k].record()
+        return previous
+
+
+def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, step_per_epoch, rank, world, device, best_path,
+                last_path):
+    """The reference's training structure ([3P] tianshou ``OffpolicyTrainer`` as l_dgn.py:246-261 configures it): evaluate, then
+    ``epoch`` times [update iterations until ``step_per_epoch`` more env steps are collected; evaluate; keep the best policy], then
+    save the last one.  env steps = decisions x ``world``, the decisions being this rank's - with several ranks the smallest
+    rank's, a number all of them hold (:func:`_agreed_decisions`), so that targets and counts, and with them the number of updates
+    of every epoch, are the same everywhere.  The end of an epoch is noticed from a count that is one iteration old
+    (:class:`_StaleDecisionCount`), so an epoch runs one iteration past its target: ``overshoot`` env steps.
+    ``before_first_epoch()`` runs after the first evaluation (the update's capture, whose warm-up updates that evaluation and
+    the first ``_best.pth`` must not see).  Rank 0 evaluates and writes; the others wait at the barrier; every rank keeps the
+    epochs' counters.  -> (losses [first, last], training seconds, updates, result)"""
+    import torch
+    from . import parallel
+    if rank == 0:
+        os.makedirs(os.path.dirname(best_path), exist_ok=True)
+    epochs, best = [], None
+
+    def test(index, env_step, **more):
+        nonlocal best
+        rec = dict(epoch=index, env_step=env_step, eps=loop.eps_now()[1], **more)
+        stats = evaluate()
+        if rank == 0:
+            is_best = best is None or stats["rew"] > best[1]   # (the first evaluation sets the best: [3P] BaseTrainer.reset)
+            if is_best:
+                best = (index, stats["rew"])
+                torch.save(policy.state_dict(), best_path)     # save_best_fn, l_dgn.py:215-222
+            rec.update(test_rew=stats["rew"], test_len=stats["len"], best=is_best)
+            rec.update({k: v for k, v in stats.items() if k not in ("rew", "len")})
+        epochs.append(rec)
+        parallel.barrier()
+
+    env_step = _agreed_decisions(loop, world, device) * world
+    test(0, env_step, overshoot=0, updates=0, seconds=0.0)
+    before_first_epoch()
+    stale = _StaleDecisionCount(loop, world)
+    first = last = None
+    updates, seconds = 0, 0.0
+    for e in range(1, epoch + 1):
+        target = env_step + step_per_epoch
+        n, t0 = 0, time.perf_counter()
+        while True:
+            last = iteration(updates + n)
+            first = last if first is None else first
+            n += 1
+            seen = stale.push()
+            if seen is not None and seen * world >= target:
+                break
+        env_step = _agreed_decisions(loop, world, device) * world     # (synchronises: the epoch is over)
+        dt = time.perf_counter() - t0
+        updates, seconds = updates + n, seconds + dt
+        test(e, env_step, overshoot=env_step - target, updates=n, seconds=dt)
+    if rank == 0:
+        torch.save(policy.state_dict(), last_path)             # l_dgn.py:263-266
+    parallel.barrier()
+    best = best if best is not None else (None, None)
+    return [first, last], seconds, updates, dict(epochs=epochs, best_epoch=best[0], best_rew=best[1], best_path=best_path,
+                                                 last_path=last_path)
+
+
 def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4, batch_size=32, n_step=4,
           gamma=0.99, lr=1e-3, target_update_freq=500, eps=0.1, replay_rounds=64, seed=9, backend=None, log=print,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
-          heuristic=None, scripted_agents_ratio=0.0):
+          heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
+          exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -68,10 +212,16 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     :class:`melissa_amd.replay.PrioritizedRoundReplay` (each rank owns its buffer; nothing more is exchanged).
     ``heuristic`` / ``scripted_agents_ratio``: the reference's ``--heuristic --scripted-agents-ratio`` (common.py:67,69; every
     training script hands them to its training envs, l_dgn.py:137-146): that fraction of the nodes, drawn anew on every reset
-    by the device episode stream (core.py:197-217,395), runs the heuristic instead of the policy and is never recorded."""
+    by the device episode stream (core.py:197-217,395), runs the heuristic instead of the policy and is never recorded.
+    ``epoch``: None (the default) runs ``updates`` updates at the constant ``eps`` - the fixed-updates mode.  A number runs the
+    reference's training structure instead (``OffpolicyTrainer`` as l_dgn.py:246-261 configures it; see :func:`_run_epochs`):
+    ``epoch`` epochs of ``step_per_epoch`` env steps, eps decaying on the device from ``eps_train`` to ``eps_train_final`` over
+    ``exploration_fraction`` of the run, ``test_num`` evaluation episodes at ``eps_test`` before the first epoch and after every
+    epoch, ``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth`` checkpoints (``policy.state_dict()``).
+    ``resume_path``: start from the weights of such a file (weights only, as the reference's ``--resume-path``)."""
     import torch
     from . import launch, parallel
-    from .collect import RoundLoop
+    from .collect import EpsSchedule, RoundLoop
     from .env import HipGraphVectorEnv, synthetic_graph_pool
     from .replay import PrioritizedRoundReplay, RoundReplay
     if backend != "gloo":
@@ -85,6 +235,11 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     policy_cls, learner_cls, neighbours = policy_and_learner(model)
     policy = policy_cls(net, torch.optim.Adam(net.parameters(), lr=lr), discount_factor=gamma,
                         estimation_step=n_step, target_update_freq=target_update_freq)
+    if resume_path is not None:
+        # --resume-path (l_dgn.py:311 load_policy): the weights of a saved policy, model.* and model_old.*, nothing else
+        policy.load_state_dict(torch.load(resume_path, map_location=device, weights_only=True))
+        parallel.broadcast_parameters(net, src=0)
+    checksum_start = _param_checksum(net) if epoch is not None else None      # (what the first update starts from)
     from .env import cached_graph_pool
     graph_list = cached_graph_pool(n_nodes, graphs, 0) if graphs >= 4096 else synthetic_graph_pool(n_nodes, graphs, first_seed=0)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
@@ -95,8 +250,15 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     else:
         replay = RoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours)
     # the rounds between two updates replay from one HIP graph (bit-identical to the eager launches: tests/test_gpu_round.py)
+    schedule = None
+    if epoch is not None:
+        # training rounds take eps from the device schedule; every rank collects as much again, so a decision here is `world`
+        # env steps of the run
+        schedule = EpsSchedule(eps_train=eps_train, eps_final=eps_train_final, exploration_fraction=exploration_fraction,
+                               epoch=int(epoch), step_per_epoch=int(step_per_epoch), scale=world)
     loop = RoundLoop(venv, policy, seed=1000 + rank * envs, eps=eps, replay=replay, ring=ring,
-                     use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update))
+                     use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update),
+                     eps_schedule=schedule)
     learner = learner_cls(policy, replay, batch_size=batch_size, n_step=n_step, gamma=gamma,
                          grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank)
     with torch.no_grad():
@@ -106,25 +268,45 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         # step), so RCCL never enters a capture; rehearsed with two ranks on one GPU (tests/test_gpu_round.py)
         capture_updates = probe is None
     captured = bool(capture_updates) and device.type == "cuda"
-    warmup_updates = 0
-    if captured:
-        learner.capture()                                      # (two warm-up updates, then the graphs)
-        warmup_updates = 2
-    t0 = time.perf_counter()
-    losses = []
-    for _ in range(updates):
+    warmup_updates = 2 if captured else 0
+
+    def capture():
+        if captured:
+            learner.capture()                                  # (two warm-up updates, then the graphs)
+
+    if epoch is None:
+        capture()
+    def iteration(index):
+        """``rounds_per_update`` rounds, then one update; -> its loss (a device tensor when the update is replayed from graphs)"""
         with torch.no_grad():
             loop.run(rounds_per_update)
         if probe is not None:
-            probe(len(losses), net, learner, "before")
-        losses.append(learner.step()["loss"])
+            probe(index, net, learner, "before")
+        loss = learner.step()["loss"]
         if probe is not None:
-            probe(len(losses) - 1, net, learner, "after")
-    torch.cuda.synchronize(device)
-    dt = time.perf_counter() - t0
+            probe(index, net, learner, "after")
+        return loss
+
+    extra = {}
+    if epoch is None:
+        t0 = time.perf_counter()
+        losses = [iteration(i) for i in range(updates)]
+        torch.cuda.synchronize(device)
+        dt = time.perf_counter() - t0
+    else:
+        def evaluate():
+            return _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scripted_agents_ratio) if rank == 0 else None
+        weights_dir = os.path.join(logdir, model, "weights")
+        name = model_name if model_name is not None else default_model_name()
+        # (epoch mode captures the update AFTER the first evaluation: `param_checksum_start`, that evaluation and the first
+        # _best.pth are all of the policy no update has touched)
+        losses, dt, updates, extra = _run_epochs(loop, policy, iteration, evaluate, capture, int(epoch), int(step_per_epoch), rank,
+                                                 world, device, os.path.join(weights_dir, f"{name}_best.pth"),
+                                                 os.path.join(weights_dir, f"{name}_last.pth"))
+        extra["param_checksum_start"] = checksum_start
     losses = [float(x) for x in losses]                        # (device tensors when the update is replayed from graphs)
     c = loop.counters()
-    checksum = float(torch.cat([p.detach().flatten() for p in net.parameters()]).double().sum())
+    checksum = _param_checksum(net)
     out = dict(rank=rank, world=world, model=model, updates=updates, seconds=dt, loss_first=losses[0],
                loss_last=losses[-1], decisions=c["decisions"], episodes=c["episodes"], errors=c["errors"],
                param_checksum=checksum, updates_from_hip_graphs=captured, prio_buffer=bool(prio_buffer),
@@ -133,6 +315,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                # warmup_updates` steps, `seconds` covers `updates` of them
                warmup_updates=warmup_updates, heuristic=heuristic, scripted_agents_ratio=float(scripted_agents_ratio),
                episode_supply=loop.supply.describe())
+    out.update(extra)
     # replicas must be identical after averaged-gradient steps
     same = parallel.all_reduce_max(checksum, device) == parallel.all_reduce_max(-checksum, device) * -1
     out["replicas_identical"] = bool(same)
@@ -165,22 +348,47 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="heuristic the scripted agents run")
     ap.add_argument("--scripted-agents-ratio", type=float, default=0.0,
                     help="fraction of the nodes that are scripted agents, drawn anew for every episode")
+    # the reference's training structure, names and defaults (common.py:20-39,46,54); --epoch absent: the fixed-updates mode
+    ap.add_argument("--epoch", type=int, default=None,
+                    help="train in epochs like the reference (whose default is 10): eps decay, evaluation and checkpoints; "
+                         "--updates and the constant eps do not apply")
+    ap.add_argument("--step-per-epoch", type=int, default=100000)
+    ap.add_argument("--eps-train", type=float, default=1.0)
+    ap.add_argument("--eps-train-final", type=float, default=0.05)
+    ap.add_argument("--exploration-fraction", type=float, default=0.6)
+    ap.add_argument("--eps-test", type=float, default=0.001)
+    ap.add_argument("--test-num", type=int, default=100)
+    ap.add_argument("--logdir", type=str, default="log")
+    ap.add_argument("--model-name", type=str, default=default_model_name())
+    ap.add_argument("--resume-path", type=str, default=None)
+    ap.add_argument("--seed", type=int, default=9)
+    ap.add_argument("--lr", type=float, default=0.001)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--n-step", type=int, default=4)
+    ap.add_argument("--target-update-freq", type=int, default=500)
     return ap
+
+
+def train_kwargs(a: argparse.Namespace) -> dict:
+    """The keyword arguments of :func:`train` a parsed command line stands for (``epoch`` None = the fixed-updates mode)."""
+    return dict(model=a.model, n_nodes=a.nodes, envs=a.envs, updates=a.updates, rounds_per_update=a.rounds_per_update,
+                batch_size=a.batch_size, backend=a.backend, graphs=a.graphs,
+                capture_updates={"auto": None, "on": True, "off": False}[a.capture_updates],
+                prio_buffer=a.prio_buffer, alpha=a.alpha, beta=a.beta, heuristic=a.heuristic,
+                scripted_agents_ratio=a.scripted_agents_ratio, epoch=a.epoch, step_per_epoch=a.step_per_epoch,
+                eps_train=a.eps_train, eps_train_final=a.eps_train_final, exploration_fraction=a.exploration_fraction,
+                eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
+                seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq)
 
 
 def main():
     a = arg_parser().parse_args()
-    import os
     import sys
     from . import launch
     rc = launch.maybe_spawn("-m", ["melissa_amd.train", *sys.argv[1:]], a.gpus, check_devices=a.backend != "gloo")
     if rc is not None:
         raise SystemExit(rc)
-    train(model=a.model, n_nodes=a.nodes, envs=a.envs, updates=a.updates, rounds_per_update=a.rounds_per_update,
-          batch_size=a.batch_size, backend=a.backend, graphs=a.graphs,
-          capture_updates={"auto": None, "on": True, "off": False}[a.capture_updates],
-          prio_buffer=a.prio_buffer, alpha=a.alpha, beta=a.beta, heuristic=a.heuristic,
-          scripted_agents_ratio=a.scripted_agents_ratio)
+    train(**train_kwargs(a))
 
 
 if __name__ == "__main__":

@@ -5,7 +5,8 @@ run test episodes on evaluation envs, report the episodes' statistics).
                                 [--heuristic mpr --scripted-agents-ratio 0.5]
 
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
-``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by the reference's trainer (keys ``model.*`` /
+``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by ``python -m melissa_amd.train --epoch ...``
+(``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth``) or by the reference's trainer (keys ``model.*`` /
 ``model_old.*``, l_dgn.py:311), loaded with ``weights_only=True``.  ``--heuristic`` / ``--scripted-agents-ratio`` are the
 reference's flags (common.py:67,69): that fraction of the nodes runs the heuristic instead of the policy (in the evaluation
 schedule the policy still decides for them, graph.py:244,340; the heuristic overrides it inside the world step).
@@ -20,7 +21,7 @@ import torch
 from .collect import Collector
 from .env import HipGraphVectorEnv, synthetic_graph_pool
 from .policy import DQNPolicy
-from .train import build_network
+from .train import N_DGN_NETWORK, build_network
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
@@ -47,7 +48,8 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="l_dgn", choices=["l_dgn", "hl_dgn", "dgn_r"])
+    # (the three N-DGN scripts train these networks under their own names: a checkpoint of theirs loads into the same classes)
+    ap.add_argument("--model", default="l_dgn", choices=["l_dgn", "hl_dgn", "dgn_r", *N_DGN_NETWORK])
     ap.add_argument("--nodes", type=int, default=20)
     ap.add_argument("--envs", type=int, default=1)
     ap.add_argument("--episodes", type=int, default=10)
