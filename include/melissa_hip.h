@@ -750,6 +750,35 @@ typedef struct mel_adam_tensors {
 mel_status mel_adam_step(const mel_adam_tensors* t, float lr, float beta1, float beta2, float eps, float weight_decay,
                          double host_step, void* stream);
 
+/* The TD target and the TD loss of one update, one launch each: what a torch formulation spends ~20 one-line launches on (index /
+ * sub / pow / mean / mul and their autograd backward nodes; argmax / gather / mul / add on the target side).  All buffers device
+ * fp32 unless said otherwise, row-major; no float atomics, every sum in a fixed order - two calls on the same inputs give the same
+ * bits; no host value changes between two calls of an update, so both replay from a HIP graph.
+ *
+ * mel_td_target ([3P] DQNPolicy._target_q + compute_nstep_return as l_dgn.py:70-78 configures them: is_double, estimation_step):
+ *   best_i = q_target[i, argmax_a q_online[i, a]] (double DQN; the lowest index wins a tie) or max_a q_target[i, a] when q_online is
+ *   NULL; returns_i = ret_i + boot_w_i * best_i, the product and the sum rounded separately (no fused multiply-add): the bits of the
+ *   torch expression.  q_target / q_online [batch, n_actions], ret / boot_w / returns [batch].
+ * mel_td_loss ([3P] DQNPolicy.learn with n_nodes = 1 and member = NULL: q = logits [batch, n_actions]; policies/dgn.py:43-64 and
+ *   policies/n_dgn.py:36-66 with member = the siblings summed over, [batch, n_nodes] floats, 0 = not a sibling):
+ *     batch_q_i = sum_j member_ij q[i, j, act_ij]        td_i = returns_i - batch_q_i
+ *     loss = mean_i weight_i td_i^2   (huber = 0; weight NULL = 1)   or   huber_loss(batch_q, returns), delta = 1, mean, weight unused
+ *     dq[i, j, a] = d loss / d q[i, j, a]: -2 weight_i td_i / batch at (j, a = act_ij) of a sibling, 0 elsewhere - EVERY element is
+ *     written, dq needs no memset.
+ *   q / dq [batch, n_nodes, n_actions], act device int64 [batch, n_nodes] (an action outside [0, n_actions) counts as no sibling),
+ *   loss [1], td [batch].  scratch: device memory of (batch + MEL_TD_GROUP_ROWS - 1) / MEL_TD_GROUP_ROWS floats - the workgroups'
+ *   partial sums, added in index order by a second small launch; unused (may be NULL) when that is one.
+ * MEL_ERR_INVALID_ARG: a null pointer, batch outside [1, MEL_TD_MAX_BATCH], n_actions outside [1, MEL_TD_MAX_ACTIONS], n_nodes outside
+ * [1, MEL_MAX_NODES]; MEL_ERR_WORKSPACE: scratch_bytes below what the batch needs. */
+#define MEL_TD_GROUP_ROWS 64
+#define MEL_TD_MAX_BATCH 65536
+#define MEL_TD_MAX_ACTIONS 8
+mel_status mel_td_target(const float* q_target, const float* q_online, const float* ret, const float* boot_w, int64_t batch,
+                         int32_t n_actions, float* returns, void* stream);
+mel_status mel_td_loss(const float* q, const int64_t* act, const float* member, const float* returns, const float* weight,
+                       int64_t batch, int32_t n_nodes, int32_t n_actions, int32_t huber, float* loss, float* td, float* dq,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 /* One whole env ROUND per launch for every env of the batch (round-batched loop): replays, in the
  * reference's AEC order, the dead-agent steps and one GraphEnv.step per active agent with that agent's
  * action until the world step fires or the episode ends (then the env is reset to

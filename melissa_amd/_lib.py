@@ -8,6 +8,7 @@ import os
 from . import build as _build
 
 MAX_HEAD_LAYERS = 6
+TD_GROUP_ROWS, TD_MAX_BATCH, TD_MAX_ACTIONS = 64, 65536, 8      # MEL_TD_*: mel_td_target / mel_td_loss
 MAX_NODES = 128              # MEL_MAX_NODES: one wavefront per graph, one or two nodes per lane, node sets = 1 or 2 uint64 words
 
 
@@ -40,7 +41,7 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
-           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule")
+           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -250,6 +251,10 @@ def load(build_if_missing: bool = True):
     lib.mel_env_round.argtypes = [E, P, vp, vp, vp, vp, i32, i32, vp, C.POINTER(MelRoundReplay), vp]
     lib.mel_adam_step.restype = i32
     lib.mel_adam_step.argtypes = [C.POINTER(MelAdamTensors), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double, vp]
+    lib.mel_td_target.restype = i32
+    lib.mel_td_target.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
+    lib.mel_td_loss.restype = i32
+    lib.mel_td_loss.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp]
     lib.mel_replay_sample.restype = i32
     lib.mel_replay_sample.argtypes = [C.POINTER(MelRoundReplay), i64, i32, i32, i32, C.POINTER(C.c_float), C.c_uint64, vp, vp,
                                       C.POINTER(MelReplayBatch), vp]

@@ -564,3 +564,5 @@ mel_status mel_pool_backward(const float* grad_pooled, const float* dm, const in
 }
 
 }  // extern "C"
+
+#include "td.hpp"      // mel_td_target / mel_td_loss: the TD target and the TD loss with its seed gradient, one launch each

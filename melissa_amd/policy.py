@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from . import _lib
 from .optim import adam_step
+from .td import td_loss
 
 
 class Batch(dict):
@@ -112,26 +113,36 @@ class DQNPolicy(nn.Module):
         return act
 
     # ------------------------------------------------------------------ learning (autograd path)
-    def learn(self, batch, grad_hook=None) -> dict:
+    def learn(self, batch, grad_hook=None, fused_td: bool = False) -> dict:
         """One DQN update on ``batch`` = dict(obs, act, returns[, weight]).  ``grad_hook(model)`` runs
         between backward and the optimizer step (the RCCL gradient all-reduce plugs in here).  ``batch["td_error"]`` is set to
-        ``returns - q`` (what [3P] hands the prioritized buffer in ``batch.weight``)."""
+        ``returns - q`` (what [3P] hands the prioritized buffer in ``batch.weight``).  ``fused_td``: see :meth:`loss_backward`."""
         if self._target and self._iter % self._freq == 0:
             self.sync_weight()
-        loss = self.loss_backward(batch)
+        loss = self.loss_backward(batch, fused_td=fused_td)
         if grad_hook is not None:
             grad_hook(self.model)
         adam_step(self.optim)      # torch.optim.Adam's update on its own state, one launch (melissa_amd.optim)
         self._iter += 1
         return {"loss": float(loss)}
 
-    def loss_backward(self, batch) -> torch.Tensor:
+    def loss_backward(self, batch, fused_td: bool = False) -> torch.Tensor:
         """zero_grad + forward + loss + backward of one update; returns the detached loss (a device tensor: no host
-        synchronisation here, so that a captured update - melissa_amd.replay.CapturedUpdate - can contain it)."""
+        synchronisation here, so that a captured update - melissa_amd.replay.CapturedUpdate - can contain it).
+        ``fused_td`` (device tensors only; host tensors keep the torch expressions below): loss, TD error and the gradient of
+        the loss with respect to the logits come from ONE launch (``mel_td_loss``) and backpropagation starts from that
+        gradient - the same values without the dozen one-line launches of the expressions and their autograd nodes."""
         self.optim.zero_grad(set_to_none=True)
         with torch.enable_grad():
             logits, _ = self.model(batch["obs"])
             act = torch.as_tensor(batch["act"], device=logits.device, dtype=torch.long)
+            if fused_td and logits.is_cuda:
+                weight = batch.get("weight") if isinstance(batch, dict) else None
+                loss, td, dq = td_loss(logits, act, None, batch["returns"], weight, huber=self._clip_loss_grad)
+                torch.autograd.backward(logits, dq)
+                if isinstance(batch, dict):
+                    batch["td_error"] = td
+                return loss
             q = logits[torch.arange(len(act), device=logits.device), act]
             returns = torch.as_tensor(batch["returns"], device=logits.device, dtype=q.dtype).flatten()
             td = returns - q
@@ -160,23 +171,26 @@ class DGNPolicy(DQNPolicy):
     dgn.py:31-55); here ALL sibling observations of the batch go through ONE forward and a segment sum
     (SURVEY.md 8(f) #3).  Same loss value and gradients (tests/test_host_logic.py compares with the loop)."""
 
-    def learn(self, batch, grad_hook=None) -> dict:
+    def learn(self, batch, grad_hook=None, fused_td: bool = False) -> dict:
         """batch: ``returns`` [B] and EITHER the reference's row form - ``active_obs`` [M, 8N+1] (all sibling observations,
         index column = the sibling), ``active_act`` [M], ``segment`` [M] = experience each sibling row belongs to - OR the
         dense form ``obs_matrix`` [B, 8N], ``act_all`` [B, N], ``sibling`` [B, N] (who acted in the sampled round): the same
-        loss, one graph evaluation per experience instead of one per sibling.  Optional ``weight``."""
+        loss, one graph evaluation per experience instead of one per sibling.  Optional ``weight``.  ``fused_td``: see
+        :meth:`loss_backward`."""
         if self._target and self._iter % self._freq == 0:
             self.sync_weight()
-        loss = self.loss_backward(batch)
+        loss = self.loss_backward(batch, fused_td=fused_td)
         if grad_hook is not None:
             grad_hook(self.model)
         adam_step(self.optim)      # torch.optim.Adam's update on its own state, one launch (melissa_amd.optim)
         self._iter += 1
         return {"loss": float(loss)}
 
-    def loss_backward(self, batch) -> torch.Tensor:
+    def loss_backward(self, batch, fused_td: bool = False) -> torch.Tensor:
         """zero_grad + forward + DGN loss + backward; returns the detached loss (a device tensor, no host synchronisation:
-        the dense form has static shapes and can be captured by replay.CapturedUpdate)."""
+        the dense form has static shapes and can be captured by replay.CapturedUpdate).  ``fused_td`` (the dense form on device
+        tensors; the row form and host tensors keep the torch expressions): sibling sum, loss, TD error and the gradient with
+        respect to ``q_all`` in ONE launch (``mel_td_loss``), backpropagation starts from that gradient."""
         self.optim.zero_grad(set_to_none=True)
         with torch.enable_grad():
             if "obs_matrix" in batch:
@@ -184,6 +198,13 @@ class DGNPolicy(DQNPolicy):
                 dev = q_all.device
                 act = torch.as_tensor(batch["act_all"], device=dev, dtype=torch.long)
                 sib = torch.as_tensor(batch["sibling"], device=dev).to(q_all.dtype)
+                if fused_td and q_all.is_cuda:
+                    weight = batch.get("weight") if isinstance(batch, dict) else None
+                    loss, td, dq = td_loss(q_all, act, sib, batch["returns"], weight, huber=self._clip_loss_grad)
+                    torch.autograd.backward(q_all, dq)
+                    if isinstance(batch, dict):
+                        batch["td_error"] = td
+                    return loss
                 returns = torch.as_tensor(batch["returns"], device=dev, dtype=q_all.dtype).flatten()
                 q = q_all.gather(2, act[..., None]).squeeze(2)                                  # [B, N]
                 batch_q = (q * sib).sum(dim=1)                                                  # dgn.py:43-55
@@ -243,7 +264,7 @@ class NDGNPolicy(DGNPolicy):
     ``active_obs`` [M, 8N+1] with ``active_index`` [M] (active_obs.index; default: every valid entry of ``indices`` in row order,
     as collaborative_shared_policy.py:55-59 gathers them) and ``active_act`` [M]."""
 
-    def loss_backward(self, batch) -> torch.Tensor:
+    def loss_backward(self, batch, fused_td: bool = False) -> torch.Tensor:
         if isinstance(batch, dict) and "obs_matrix" not in batch and "segment" not in batch:
             indices = np.asarray(batch["indices"])
             active_index = batch.get("active_index")            # (collaborative_shared_policy.py:55-59 stacks every valid index)
@@ -260,7 +281,7 @@ class NDGNPolicy(DGNPolicy):
             batch["weight"] = rows["weight"]                    # prio-buffer hook, n_dgn.py:67
             batch["td_error"] = rows["td_error"]
             return loss
-        return super().loss_backward(batch)
+        return super().loss_backward(batch, fused_td=fused_td)
 
     @staticmethod
     def neighbour_indices(indices: np.ndarray, active_one_hop_neighbors: np.ndarray, agent_id) -> np.ndarray:

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .optim import adam_step
+from .td import td_target
 
 
 class RoundReplay:
@@ -331,28 +332,42 @@ class DQNLearner:
     """n-step DQN update over a :class:`RoundReplay` (the learn half of the reference's training loop,
     l_dgn.py:246-261 -> [3P] DQNPolicy.process_fn / learn): target = ret + boot_w * max_a Q_target(boot_obs)
     with the target network evaluated by the HIP forward, then one autograd step (``grad_hook`` = the flat
-    RCCL gradient all-reduce of melissa_amd.parallel)."""
+    RCCL gradient all-reduce of melissa_amd.parallel).  ``fused_td``: the target's argmax / gather / mul / add and the loss with its
+    seed gradient are one HIP launch each (``mel_td_target`` / ``mel_td_loss``, :mod:`melissa_amd.td`) instead of torch expressions -
+    on device tensors, eagerly and inside a captured update; off by default, so every existing caller keeps its launches."""
 
     def __init__(self, policy, replay: RoundReplay, batch_size: int = 32, n_step: int = 4, gamma: float = 0.99,
-                 grad_hook=None, seed: int = 0):
-        self.policy, self.replay = policy, replay
+                 grad_hook=None, seed: int = 0, fused_td: bool = False):
+        self.policy, self.replay, self.fused_td = policy, replay, bool(fused_td)
         self.batch_size, self.n_step, self.gamma, self.grad_hook = batch_size, n_step, gamma, grad_hook
         self.gen = torch.Generator(device=replay.obs.device)
         self.gen.manual_seed(seed)
         self.captured = None
 
-    def sample_batch(self) -> dict:
-        """Sample + n-step targets: dict(obs, act, returns) of device tensors, no host synchronisation."""
-        b = self.replay.sample(self.batch_size, self.n_step, self.gamma, self.gen)
+    def _returns(self, b: dict) -> torch.Tensor:
+        """n-step targets of a sampled batch: ``ret + boot_w * Q_target(boot_obs)[best action]`` [bs]."""
         with torch.no_grad():
             target_net = self.policy.model_old if getattr(self.policy, "_target", False) else self.policy.model
-            q_next = target_net.hip_forward(b["boot_obs"]) if b["boot_obs"].is_cuda else target_net.torch_forward(b["boot_obs"])
-            if self.policy._is_double:                      # double DQN: argmax from the online net
-                online = self.policy.model.hip_forward(b["boot_obs"]) if b["boot_obs"].is_cuda else self.policy.model.torch_forward(b["boot_obs"])
+            fwd = (lambda net, o: net.hip_forward(o)) if b["boot_obs"].is_cuda else (lambda net, o: net.torch_forward(o))
+            q_next = fwd(target_net, b["boot_obs"])
+            online = fwd(self.policy.model, b["boot_obs"]) if self.policy._is_double else None     # double DQN: the online net's argmax
+            if self.fused_td and q_next.is_cuda:
+                return td_target(q_next, online, b["ret"], b["boot_w"])
+            if online is not None:
                 best = q_next.gather(1, online.argmax(dim=1, keepdim=True)).squeeze(1)
             else:
                 best = q_next.max(dim=1).values
-            returns = b["ret"] + b["boot_w"] * best
+            return b["ret"] + b["boot_w"] * best
+
+    def _policy_kwargs(self) -> dict:
+        """What ``policy.learn`` / ``policy.loss_backward`` get on top of the batch (nothing unless ``fused_td``: policies behind
+        this learner need not know the switch)."""
+        return {"fused_td": True} if self.fused_td else {}
+
+    def sample_batch(self) -> dict:
+        """Sample + n-step targets: dict(obs, act, returns) of device tensors, no host synchronisation."""
+        b = self.replay.sample(self.batch_size, self.n_step, self.gamma, self.gen)
+        returns = self._returns(b)
         # (boot_obs / ret / boot_w: what `returns` was built from - tests recompute it through the target network)
         out = dict(obs=b["obs"], act=b["act"], returns=returns, boot_obs=b["boot_obs"], ret=b["ret"], boot_w=b["boot_w"])
         return self._with_priority_keys(out, b)
@@ -381,7 +396,7 @@ class DQNLearner:
             if self.grad_hook is not None:
                 self.grad_hook(model)
 
-        out = self.policy.learn(work, grad_hook=hook if "weight" in work else self.grad_hook)
+        out = self.policy.learn(work, grad_hook=hook if "weight" in work else self.grad_hook, **self._policy_kwargs())
         if "td_error" in work:
             self.last_batch["td_error"] = work["td_error"]
         return out
@@ -441,7 +456,7 @@ class CapturedUpdate:
             for _ in range(warmup):
                 self._sync_target()
                 batch = L.sample_batch()
-                policy.loss_backward(batch)
+                policy.loss_backward(batch, **L._policy_kwargs())
                 L.write_back(batch)
                 if self.collective:
                     hook.pack(), hook.reduce(), hook.unpack()
@@ -453,7 +468,7 @@ class CapturedUpdate:
         self.graph_a.register_generator_state(L.gen)
         with torch.cuda.graph(self.graph_a):
             self.batch = L.sample_batch()
-            self.loss = policy.loss_backward(self.batch)
+            self.loss = policy.loss_backward(self.batch, **L._policy_kwargs())
             L.write_back(self.batch)                        # (prioritized replay: the next replay samples by what this one wrote)
             if self.collective:
                 hook.pack()
@@ -507,15 +522,7 @@ class DGNLearner(DQNLearner):
 
     def _dense_batch(self, b: dict) -> dict:
         e, k = b["env"], b["slot"]
-        with torch.no_grad():
-            target_net = self.policy.model_old if getattr(self.policy, "_target", False) else self.policy.model
-            fwd = (lambda net, o: net.hip_forward(o)) if b["boot_obs"].is_cuda else (lambda net, o: net.torch_forward(o))
-            q_next = fwd(target_net, b["boot_obs"])
-            if self.policy._is_double:
-                best = q_next.gather(1, fwd(self.policy.model, b["boot_obs"]).argmax(dim=1, keepdim=True)).squeeze(1)
-            else:
-                best = q_next.max(dim=1).values
-            returns = b["ret"] + b["boot_w"] * best
+        returns = self._returns(b)
         out = dict(obs_matrix=self.replay.obs[e, k], act_all=self.replay.act[e, k].long(),
                    sibling=self.replay._members(self.replay.acted[e, k]), returns=returns, boot_obs=b["boot_obs"], ret=b["ret"],
                    boot_w=b["boot_w"], env=e, slot=k)

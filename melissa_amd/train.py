@@ -13,6 +13,7 @@ from __future__ import annotations
 import argparse
 import datetime
 import json
+import math
 import os
 import time
 
@@ -136,8 +137,34 @@ class _StaleDecisionCount:
         return previous
 
 
+def updates_owed(env_step: int, base: int, done: int, update_per_step: float) -> int:
+    """Updates to run now, ``env_step`` env steps into a run that counts from ``base`` and has taken ``done`` updates: what brings
+    the total to ``floor(update_per_step * (env_step - base))``, never less than 0 (a count that has not moved past the updates
+    already taken owes nothing).
+
+    The reference's trainer ([3P] tianshou ``OffpolicyTrainer.policy_update_fn``) takes ``round(update_per_step * n_collected)``
+    updates after every collect, rounding collect by collect.  This rule is the cumulative floor instead: the two agree where
+    ``update_per_step * step_per_collect`` is a whole number (the reference's defaults, 0.1 * 10 = one update per collect), and
+    for every other value the cumulative form neither drifts away from ``update_per_step`` updates per env step nor depends on how
+    the run is cut into collects - summed over any split of a run into iterations it ends at the same total."""
+    return max(0, int(math.floor(update_per_step * (env_step - base))) - int(done))
+
+
+def rounds_per_collect(step_per_collect: int, envs: int, world: int = 1) -> int:
+    """``--step-per-collect`` in rounds: a round steps every env of every rank, so ``ceil(S / (envs * world))`` of them, at least
+    one, collect ``S`` env steps (a static number: the rounds of an iteration still replay from one HIP graph)."""
+    return max(1, -(-int(step_per_collect) // (int(envs) * int(world))))
+
+
+def replay_rounds_for(buffer_size: int, envs: int, n_nodes: int) -> int:
+    """``--buffer-size`` in rounds per env.  The reference splits its buffer into one sub-buffer per (env, agent) of
+    ``buffer_size / (envs * n_nodes)`` transitions (125 at its defaults: 100 000 / (40 * 20)); an agent acts at most once per
+    round, so a ring of that many rounds holds at least that many of its transitions.  Never below 8 (the pre-fill)."""
+    return max(8, -(-int(buffer_size) // (int(envs) * int(n_nodes))))
+
+
 def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, step_per_epoch, rank, world, device, best_path,
-                last_path):
+                last_path, pace=None):
     """The reference's training structure ([3P] tianshou ``OffpolicyTrainer`` as l_dgn.py:246-261 configures it): evaluate, then
     ``epoch`` times [update iterations until ``step_per_epoch`` more env steps are collected; evaluate; keep the best policy], then
     save the last one.  env steps = decisions x ``world``, the decisions being this rank's - with several ranks the smallest
@@ -146,7 +173,14 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     (:class:`_StaleDecisionCount`), so an epoch runs one iteration past its target: ``overshoot`` env steps.
     ``before_first_epoch()`` runs after the first evaluation (the update's capture, whose warm-up updates that evaluation and
     the first ``_best.pth`` must not see).  Rank 0 evaluates and writes; the others wait at the barrier; every rank keeps the
-    epochs' counters.  -> (losses [first, last], training seconds, updates, result)"""
+    epochs' counters.  -> (losses [first, last], training seconds, updates, result)
+
+    ``pace`` = (collect, update, update_per_step) switches to updates paced by env steps (``--update-per-step``): an iteration is
+    ``collect()`` followed by as many ``update(index)`` as the stale count owes (:func:`updates_owed`, counted from the first
+    evaluation's env step; 0 or many), and at the end of an epoch the count read with a synchronise settles the rest before
+    the evaluation - ``updates_done == floor(update_per_step * (env_step - base))`` at every epoch boundary.  Every rank
+    derives the number from the same agreed count, so all take the same updates.  The target-network sync keeps counting
+    updates.  Epoch records then also carry ``update_debt`` (0)."""
     import torch
     from . import parallel
     if rank == 0:
@@ -167,39 +201,64 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
         epochs.append(rec)
         parallel.barrier()
 
-    env_step = _agreed_decisions(loop, world, device) * world
-    test(0, env_step, overshoot=0, updates=0, seconds=0.0)
+    env_step = base = _agreed_decisions(loop, world, device) * world
+    test(0, env_step, overshoot=0, updates=0, seconds=0.0, **({} if pace is None else {"update_debt": 0}))
     before_first_epoch()
     stale = _StaleDecisionCount(loop, world)
     first = last = None
-    updates, seconds = 0, 0.0
+    updates, seconds, iterations = 0, 0.0, 0
     for e in range(1, epoch + 1):
         target = env_step + step_per_epoch
-        n, t0 = 0, time.perf_counter()
-        while True:
-            last = iteration(updates + n)
-            first = last if first is None else first
-            n += 1
-            seen = stale.push()
-            if seen is not None and seen * world >= target:
-                break
-        env_step = _agreed_decisions(loop, world, device) * world     # (synchronises: the epoch is over)
+        n, t0, more = 0, time.perf_counter(), {}
+        if pace is None:
+            while True:
+                last = iteration(updates + n)
+                first = last if first is None else first
+                n += 1
+                seen = stale.push()
+                if seen is not None and seen * world >= target:
+                    break
+            env_step = _agreed_decisions(loop, world, device) * world     # (synchronises: the epoch is over)
+        else:
+            collect, update, update_per_step = pace
+
+            def settle(count):
+                nonlocal n, first, last
+                for _ in range(updates_owed(count, base, updates + n, update_per_step)):
+                    last = update(updates + n)
+                    first = last if first is None else first
+                    n += 1
+
+            while True:
+                collect()
+                iterations += 1
+                seen = stale.push()
+                if seen is not None:
+                    settle(seen * world)
+                    if seen * world >= target:
+                        break
+            env_step = _agreed_decisions(loop, world, device) * world     # (synchronises: the epoch is over)
+            settle(env_step)
+            more["update_debt"] = int(math.floor(update_per_step * (env_step - base))) - (updates + n)
         dt = time.perf_counter() - t0
         updates, seconds = updates + n, seconds + dt
-        test(e, env_step, overshoot=env_step - target, updates=n, seconds=dt)
+        test(e, env_step, overshoot=env_step - target, updates=n, seconds=dt, **more)
     if rank == 0:
         torch.save(policy.state_dict(), last_path)             # l_dgn.py:263-266
     parallel.barrier()
     best = best if best is not None else (None, None)
-    return [first, last], seconds, updates, dict(epochs=epochs, best_epoch=best[0], best_rew=best[1], best_path=best_path,
-                                                 last_path=last_path)
+    result = dict(epochs=epochs, best_epoch=best[0], best_rew=best[1], best_path=best_path, last_path=last_path)
+    if pace is not None:
+        result["env_steps_per_iteration"] = (env_step - base) / max(1, iterations)
+    return [first, last], seconds, updates, result
 
 
 def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4, batch_size=32, n_step=4,
           gamma=0.99, lr=1e-3, target_update_freq=500, eps=0.1, replay_rounds=64, seed=9, backend=None, log=print,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
           heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
-          exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None):
+          exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
+          update_per_step=None, step_per_collect=10, buffer_size=None):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -218,7 +277,23 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     ``epoch`` epochs of ``step_per_epoch`` env steps, eps decaying on the device from ``eps_train`` to ``eps_train_final`` over
     ``exploration_fraction`` of the run, ``test_num`` evaluation episodes at ``eps_test`` before the first epoch and after every
     epoch, ``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth`` checkpoints (``policy.state_dict()``).
-    ``resume_path``: start from the weights of such a file (weights only, as the reference's ``--resume-path``)."""
+    ``resume_path``: start from the weights of such a file (weights only, as the reference's ``--resume-path``).
+    ``update_per_step`` (epoch mode only, else ValueError): pace the updates by the env steps collected, the reference's
+    ``--update-per-step`` (common.py:35; 0.1 there: one update per 10 env steps) - after every iteration as many updates as
+    :func:`updates_owed` says, the rest settled at each epoch's end (:func:`_run_epochs`); the TD target and the TD loss of these
+    updates are one HIP launch each (``fused_td``, :mod:`melissa_amd.td`).  An iteration then collects ``step_per_collect`` env
+    steps (``--step-per-collect``, common.py:34: :func:`rounds_per_collect` rounds instead of ``rounds_per_update``).
+    ``buffer_size``: the reference's ``--buffer-size`` (transitions in all; :func:`replay_rounds_for` rounds per env instead of
+    ``replay_rounds``)."""
+    if update_per_step is not None:
+        if epoch is None:
+            raise ValueError("update_per_step paces the updates of the epoch mode: it needs epoch")
+        if not (float(update_per_step) > 0 and math.isfinite(float(update_per_step))):
+            raise ValueError(f"update_per_step={update_per_step} must be a positive number")
+        if int(step_per_collect) < 1:
+            raise ValueError(f"step_per_collect={step_per_collect} must be >= 1")
+    if buffer_size is not None and int(buffer_size) < 1:
+        raise ValueError(f"buffer_size={buffer_size} must be >= 1")
     import torch
     from . import launch, parallel
     from .collect import EpsSchedule, RoundLoop
@@ -245,6 +320,11 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False, heuristic=heuristic,
                              scripted_agents_ratio=scripted_agents_ratio)
+    paced = update_per_step is not None
+    if buffer_size is not None:
+        replay_rounds = replay_rounds_for(buffer_size, envs, n_nodes)
+    if paced:
+        rounds_per_update = rounds_per_collect(step_per_collect, envs, world)
     if prio_buffer:
         replay = PrioritizedRoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours, alpha=alpha, beta=beta)
     else:
@@ -260,7 +340,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                      use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update),
                      eps_schedule=schedule)
     learner = learner_cls(policy, replay, batch_size=batch_size, n_step=n_step, gamma=gamma,
-                         grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank)
+                         grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank, **({"fused_td": True} if paced else {}))
     with torch.no_grad():
         loop.run(max(n_step + 1, 8))                           # pre-fill (l_dgn.py:201)
     if capture_updates is None:
@@ -276,16 +356,23 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
 
     if epoch is None:
         capture()
-    def iteration(index):
-        """``rounds_per_update`` rounds, then one update; -> its loss (a device tensor when the update is replayed from graphs)"""
+    def collect():
         with torch.no_grad():
             loop.run(rounds_per_update)
+
+    def update(index):
+        """One update; -> its loss (a device tensor when the update is replayed from graphs)"""
         if probe is not None:
             probe(index, net, learner, "before")
         loss = learner.step()["loss"]
         if probe is not None:
             probe(index, net, learner, "after")
         return loss
+
+    def iteration(index):
+        """``rounds_per_update`` rounds, then one update; -> its loss"""
+        collect()
+        return update(index)
 
     extra = {}
     if epoch is None:
@@ -302,9 +389,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         # _best.pth are all of the policy no update has touched)
         losses, dt, updates, extra = _run_epochs(loop, policy, iteration, evaluate, capture, int(epoch), int(step_per_epoch), rank,
                                                  world, device, os.path.join(weights_dir, f"{name}_best.pth"),
-                                                 os.path.join(weights_dir, f"{name}_last.pth"))
+                                                 os.path.join(weights_dir, f"{name}_last.pth"),
+                                                 pace=(collect, update, float(update_per_step)) if paced else None)
         extra["param_checksum_start"] = checksum_start
-    losses = [float(x) for x in losses]                        # (device tensors when the update is replayed from graphs)
+        if paced:
+            extra.update(update_per_step=float(update_per_step), rounds_per_collect=rounds_per_update,
+                         replay_rounds=replay.K, fused_td=learner.fused_td)
+    # (device tensors when the update is replayed from graphs; a paced run too short to owe an update has no loss)
+    losses = [float(x) if x is not None else float("nan") for x in losses]
     c = loop.counters()
     checksum = _param_checksum(net)
     out = dict(rank=rank, world=world, model=model, updates=updates, seconds=dt, loss_first=losses[0],
@@ -329,7 +421,8 @@ def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="hl_dgn", choices=list(MODELS))
     ap.add_argument("--nodes", type=int, default=20)
-    ap.add_argument("--envs", type=int, default=256, help="envs per GPU")
+    ap.add_argument("--envs", "--training-num", dest="envs", type=int, default=256,
+                    help="envs per GPU (--training-num: the reference's name, common.py:37)")
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--rounds-per-update", type=int, default=4)
     ap.add_argument("--batch-size", type=int, default=32)
@@ -353,6 +446,13 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="train in epochs like the reference (whose default is 10): eps decay, evaluation and checkpoints; "
                          "--updates and the constant eps do not apply")
     ap.add_argument("--step-per-epoch", type=int, default=100000)
+    # update pacing, the reference's names (common.py:25,34,35); --update-per-step absent: one update per iteration
+    ap.add_argument("--update-per-step", type=float, default=None,
+                    help="updates per collected env step (the reference: 0.1); needs --epoch; the iterations then collect "
+                         "--step-per-collect env steps instead of --rounds-per-update rounds")
+    ap.add_argument("--step-per-collect", type=int, default=10, help="env steps per iteration when --update-per-step is given")
+    ap.add_argument("--buffer-size", type=int, default=None,
+                    help="replay size in transitions (the reference: 100000); absent: 64 rounds per env")
     ap.add_argument("--eps-train", type=float, default=1.0)
     ap.add_argument("--eps-train-final", type=float, default=0.05)
     ap.add_argument("--exploration-fraction", type=float, default=0.6)
@@ -378,11 +478,21 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 scripted_agents_ratio=a.scripted_agents_ratio, epoch=a.epoch, step_per_epoch=a.step_per_epoch,
                 eps_train=a.eps_train, eps_train_final=a.eps_train_final, exploration_fraction=a.exploration_fraction,
                 eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
-                seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq)
+                seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq,
+                update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size)
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The command line, with what argparse alone cannot say: ``--update-per-step`` needs ``--epoch``."""
+    ap = arg_parser()
+    a = ap.parse_args(argv)
+    if a.update_per_step is not None and a.epoch is None:
+        ap.error("--update-per-step paces the updates of the epoch mode: it needs --epoch")
+    return a
 
 
 def main():
-    a = arg_parser().parse_args()
+    a = parse_args()
     import sys
     from . import launch
     rc = launch.maybe_spawn("-m", ["melissa_amd.train", *sys.argv[1:]], a.gpus, check_devices=a.backend != "gloo")
