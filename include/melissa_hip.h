@@ -537,8 +537,19 @@ typedef struct mel_episode_pool {
  * for the new slots into the pool's snapshot batch (same code as mel_env_reset), so an ending episode loads its
  * successor's state.  With scripted agents (n_scripted > 0) the env's generator also draws World._sample_scripted_agents'
  * np_random.choice(N, n_scripted, replace=False) after the graph (core.py:197-215,395: Floyd's algorithm + the shuffle's
- * draws; the source leaves the set).  Not covered (use a host-sampled table): is_testing's fixed seed list, a fixed graph
- * that moves (its positions carry over between episodes); training mode with every node scripted is not playable.
+ * draws; the source leaves the set).
+ *
+ * The evaluation schedule (is_testing, core.py:182-187,348-370; n_test = num_test_episodes > 0): the episode seed is not
+ * drawn but read from a fixed list, test_seeds[t] = the t-th RandomState(17).randint(0, 1e9) (mel_episode_test_seeds
+ * fills it), and RandomState(test_seeds[t]) draws the graph (randint(0, n_graphs); nothing for one graph), the movement
+ * seed, the source and the interested set, whose density is not drawn: (i + 1) / 10 with i = ((t + 1) % n_test) % 10.
+ * Only the scripted set still comes from the env's generator.  Episode e of env b sits at list position
+ *     t = (b * test_env_step + (e + discarded) * test_episode_step) % n_test
+ * (0, 1): the reference's walk, every env plays the whole list from the top; (1, B): the list is spread over the B envs,
+ * env b plays positions b, b + B, ...
+ *
+ * Not covered (use a host-sampled table): a fixed graph that moves (its positions carry over between episodes);
+ * training mode with every node scripted is not playable.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct mel_graph_pool {
     int32_t n_graphs;
@@ -565,6 +576,13 @@ typedef struct mel_episode_stream {
     int32_t   reserved;
     uint64_t* draw_scripted;   /* [B, K, MEL_SET_WORDS(N)] device scratch: the drawn set per slot, source included
                                 * (core.py:395); may be NULL when n_scripted == 0                                        */
+    int32_t   n_test;          /* 0: training mode.  T > 0: the evaluation schedule over a list of T seeds (the env batch
+                                * must be in testing mode, and fixed_graph 0); draw_graph then holds list positions        */
+    int32_t   test_env_step;   /* list positions between the first episodes of env b and env b + 1                         */
+    int32_t   test_episode_step; /* list positions between two consecutive episodes of one env                            */
+    int32_t   reserved2;
+    const uint32_t* test_seeds;/* [T] device: the seed list (mel_episode_test_seeds)                                      */
+    int32_t*  test_discarded;  /* [B] device, zero at start: episodes discarded so far (they shift the walk)              */
 } mel_episode_stream;
 
 /* For every env b draw episodes produced[b], produced[b]+1, ... while the slot they go to is free - i.e. up to episode
@@ -574,7 +592,10 @@ typedef struct mel_episode_stream {
  * env is CONSTRUCTED, so that streams line up with a reference run).  `pool` must have n_episodes == B*ring, device
  * arrays the library may WRITE, a snapshot batch of B*ring envs, and produced == stream->produced.  ep_cursor is read
  * from env->scalars.  Launches on `stream`; the caller orders it against the env launches (a refill may overlap env
- * rounds on another stream as long as no env can reach an episode >= the produced[] value of the previous refill). */
+ * rounds on another stream as long as no env can reach an episode >= the produced[] value of the previous refill).
+ * With the evaluation schedule (st->n_test > 0) `discard` moves every env that many list positions on and draws the discarded
+ * episodes' scripted sets; together with a non-zero test_env_step it is an argument error.  An env batch in testing mode with
+ * n_test == 0 is MEL_ERR_UNSUPPORTED, and so is a fixed graph in testing mode. */
 /* A pacing gate for `stream`: whatever is enqueued behind it runs once the device counter `counter` (e.g. the round_counter
  * mel_env_round advances on another stream) has reached `target` (wrap-around compare), or after timeout_us.  It lets the
  * episode refill follow the main stream's progress without an event on the main stream (events between HIP-graph replays
@@ -583,6 +604,10 @@ mel_status mel_wait_counter(const uint32_t* counter, uint32_t target, uint32_t t
 
 mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool* graphs, const mel_episode_pool* pool,
                               const mel_env_batch* env, int32_t max_new, int32_t discard, void* stream);
+
+/* out[i] (device, n >= 1 words) = the i-th RandomState(17).randint(0, 1e9): the evaluation schedule's seed list
+ * (core.py:184-187), drawn by one wavefront's MT19937. */
+mel_status mel_episode_test_seeds(uint32_t* out, int32_t n, void* stream);
 
 /* Scripted agents (scripted_agents_ratio > 0): the deterministic heuristics of graph_env/env/utils/heuristics/.  The
  * probabilistic ones (probabilistic_gossip / _relay) draw from the process-global np.random: not offered. */

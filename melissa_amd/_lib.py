@@ -36,7 +36,7 @@ SET_HAS_MESSAGE, SET_ORIGIN, SET_INTERESTED, SET_SCRIPTED, SET_TRUNCATED, SET_AL
     SET_AGENTS = range(8)
 
 # every symbol include/melissa_hip.h declares
-EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_tables", "mel_prepared_weights_bytes", "mel_prepare_weights", "mel_transpose_f32", "mel_episode_refill", "mel_abi_sizeof", "mel_radius_graph", "mel_gat_forward", "mel_gat_backward", "mel_pool_forward", "mel_pool_backward",
+EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_tables", "mel_prepared_weights_bytes", "mel_prepare_weights", "mel_transpose_f32", "mel_episode_refill", "mel_episode_test_seeds", "mel_abi_sizeof", "mel_radius_graph", "mel_gat_forward", "mel_gat_backward", "mel_pool_forward", "mel_pool_backward",
            "mel_gemm_bf16", "mel_convert_bf16", "mel_hldgn_forward_envs", "mel_hldgn_forward_envs_select", "mel_plan_pointers", "mel_select_action_envs", "mel_dgnr_forward", "mel_dgnr_forward_agents", "mel_gemm_f32", "mel_gemm_f32_t", "mel_gemm_f32_splitk", "mel_gemm_f32_split", "mel_replay_sample", "mel_replay_sample_prio", "mel_replay_update_priority", "mel_adam_step", "mel_workspace_bytes", "mel_workspace_bytes_agents", "mel_ldgn_forward_agents",
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
@@ -139,7 +139,9 @@ class MelEpisodeStream(C.Structure):
                 ("fixed_interest_density", C.c_double), ("pcg", C.c_void_p), ("pcg_half", C.c_void_p),
                 ("produced", C.c_void_p), ("draw_seed", C.c_void_p), ("draw_graph", C.c_void_p), ("work", C.c_void_p),
                 ("new_count", C.c_void_p), ("n_scripted", C.c_int32), ("reserved", C.c_int32),
-                ("draw_scripted", C.c_void_p)]
+                ("draw_scripted", C.c_void_p), ("n_test", C.c_int32), ("test_env_step", C.c_int32),
+                ("test_episode_step", C.c_int32), ("reserved2", C.c_int32), ("test_seeds", C.c_void_p),
+                ("test_discarded", C.c_void_p)]
 
 
 ENV_ERR_MOVES_EXHAUSTED, ENV_ERR_NO_SELECTION, ENV_ERR_UNCOVERED_AGENT, ENV_ERR_EPISODE_UNDERRUN = 1, 2, 4, 8
@@ -281,6 +283,8 @@ def load(build_if_missing: bool = True):
     lib.mel_gemm_f32.argtypes = [vp, i32, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp]
     lib.mel_wait_counter.restype = i32
     lib.mel_wait_counter.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    lib.mel_episode_test_seeds.restype = i32
+    lib.mel_episode_test_seeds.argtypes = [vp, i32, vp]
     lib.mel_episode_refill.restype = i32
     lib.mel_episode_refill.argtypes = [C.POINTER(MelEpisodeStream), C.POINTER(MelGraphPool), P, E, i32, i32, vp]
     lib.mel_prof_create.restype = vp

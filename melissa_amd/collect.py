@@ -31,7 +31,7 @@ def sample_episode_table(venv: HipGraphVectorEnv, episodes_per_env: int, seed: i
     generator seeded ``seed + k``) -> (packed pool dict, episode_table int32 [B, K])."""
     episodes, table = [], np.zeros((venv.env_num, episodes_per_env), dtype=np.int32)
     for b in range(venv.env_num):
-        sampler = venv.make_sampler(seed + b)          # same evaluation schedule / scripted ratio / density as the env
+        sampler = venv.make_sampler(seed + b, env=b)   # same evaluation schedule / scripted ratio / density as the env
         for k in range(episodes_per_env):
             table[b, k] = len(episodes)
             episodes.append(sampler.sample())
@@ -144,11 +144,13 @@ class RoundLoop:
 
     def __init__(self, venv: HipGraphVectorEnv, policy, episodes_per_env: int = 8, seed: int = 0,
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
-                 stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: bool | None = None,
+                 stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: "bool | str | None" = None,
                  ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
-        ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes.
+        ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes;
+        ``episode_stream="test"`` streams the evaluation schedule of an env in testing mode from the device
+        (``melissa_amd.env.stream.TestEpisodeStream``; such an env gets a host-drawn table otherwise).
         ``eps_schedule`` (:class:`EpsSchedule`): every round starts with one small launch that computes eps from the envs'
         decision counters and the selection reads that device value instead of ``eps`` - eager rounds and replayed graphs
         alike, nothing is recaptured when eps changes."""
@@ -509,11 +511,13 @@ class Collector:
     vector env with ``is_testing=True`` and call ``collect(n_episode=...)``."""
 
     def __init__(self, policy, venv: HipGraphVectorEnv, episodes_per_env: int = 16, seed: int = 0, eps: float = 0.0,
-                 replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True):
+                 replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True,
+                 episode_stream: "bool | str | None" = None, ring: int = 16):
+        """``episode_stream`` / ``ring``: the episode supply, as :class:`RoundLoop` takes them."""
         self.venv, self.policy, self.chunk = venv, policy, int(chunk)
         venv.enable_episode_log(log_capacity)
         self.loop = RoundLoop(venv, policy, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=replay,
-                              use_graph=use_graph)
+                              use_graph=use_graph, episode_stream=episode_stream, ring=ring)
         self._decisions = self.loop.counters()["decisions"]
         self.collect_step, self.collect_episode, self.collect_time = 0, 0, 0.0
 
@@ -548,6 +552,68 @@ class Collector:
             self.loop.eps = eps
             self.loop._select.eps = eps
             self.loop.graph = None
+
+
+def test_shares(n_episode: int, n_envs: int) -> list:
+    """How many of the ``n_episode`` list positions env b of ``n_envs`` owns when the evaluation schedule is spread
+    (positions ``b, b + n_envs, ...`` below ``n_episode``): ``ceil((n_episode - b) / n_envs)``, 0 for envs beyond the list."""
+    return [max(0, -(-(int(n_episode) - b) // int(n_envs))) for b in range(int(n_envs))]
+
+
+test_shares.__test__ = False           # (a helper, whatever the name says to pytest)
+
+
+def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float = 0.0, seed: int = 0, use_graph: bool = True,
+                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None):
+    """One pass over the evaluation schedule with all envs of ``venv`` at once: ``venv`` is built with ``is_testing=True,
+    num_test_episodes=n_episode, spread_test_episodes=True``, so env b owns the list positions ``b, b + B, ...``
+    (:func:`test_shares`; envs beyond the list own none).  The episodes come from the device sampler
+    (:class:`melissa_amd.env.stream.TestEpisodeStream`), the rounds replay from the HIP graph in chunks of ``chunk`` until
+    every env has finished its share.  An env that is done keeps playing while the others finish (it walks on through the
+    list): those surplus episodes are dropped - of env b's rows in the episode log (they appear in play order) the first
+    share-many count, and the e-th of them is list position ``b + e * B``.
+
+    -> (:class:`CollectStatsWithInfo` with ``returns`` / ``lens`` / ``episode_info`` in list-position order, positions).
+    ``n_collected_steps`` counts every decision taken, the surplus episodes' included.  The loop is built with ``eps`` and
+    used once; calling again on the same ``venv`` starts again from the top of the list."""
+    import time
+    kw, B, T = venv._sampler_kw, venv.env_num, int(n_episode)
+    if not kw["is_testing"] or int(kw["num_test_episodes"]) != T:
+        raise ValueError(f"evaluate_spread plays the whole list once: the env needs is_testing and num_test_episodes={T}")
+    if (kw.get("test_env_step", 0), kw.get("test_episode_step", 1)) != (1, B):
+        raise ValueError("evaluate_spread needs an env built with spread_test_episodes=True")
+    shares = np.asarray(test_shares(T, B))
+    capacity = int(log_capacity) if log_capacity is not None else max(1024, 16 * (T + B))
+    t0 = time.perf_counter()
+    venv.scalars().zero_()                     # the episode cursors count from 0 again: this pass starts at the top
+    col = Collector(policy, venv, seed=seed, eps=eps, chunk=chunk, use_graph=use_graph, log_capacity=capacity,
+                    episode_stream="test", ring=ring)
+    with torch.no_grad():
+        while True:
+            col.loop.run(col.chunk)
+            sc = venv.scalars().cpu().numpy()                                     # synchronises
+            errors = int(np.bitwise_or.reduce(sc[:, _lib.S_ERROR]))
+            if errors:
+                raise RuntimeError(f"env error flags {errors:#x} (episode pool exhausted or desynchronised actions)")
+            if (sc[:, _lib.S_EPISODES_DONE] >= shares).all():
+                break
+            if int(venv.log_cursor.item()) >= capacity:
+                raise RuntimeError(f"the episode log ({capacity} rows) filled before every env finished its share of the "
+                                   f"evaluation: raise log_capacity")
+    col.loop.supply.side.synchronize()         # (the last refill may still be writing the ring this call is about to drop)
+    steps = int(sc[:, _lib.S_DECISIONS].sum()) - col._decisions
+    stats, meta, _total = venv.read_episode_log()
+    rows, positions = [], []
+    for b in range(B):
+        mine = np.flatnonzero(meta[:, 0] == b)[:shares[b]]
+        if len(mine) < shares[b]:
+            raise RuntimeError(f"the episode log ({capacity} rows) dropped rows of env {b}'s share: raise log_capacity")
+        rows.extend(mine.tolist())
+        positions.extend(b + e * B for e in range(shares[b]))
+    order = np.argsort(np.asarray(positions, dtype=np.int64), kind="stable")
+    rows, positions = np.asarray(rows, dtype=np.int64)[order], np.asarray(positions, dtype=np.int64)[order]
+    dt = max(time.perf_counter() - t0, 1e-9)
+    return result_from_episode_log(stats[rows], meta[rows], T, steps, dt), positions
 
 
 class MultiAgentCollector(Collector):

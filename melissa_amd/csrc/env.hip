@@ -1348,6 +1348,10 @@ mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool
     return launch_episode_refill(st, graphs, pool, env, max_new, discard, static_cast<hipStream_t>(stream));
 }
 
+mel_status mel_episode_test_seeds(uint32_t* out, int32_t n, void* stream) {
+    return launch_episode_test_seeds(out, n, static_cast<hipStream_t>(stream));
+}
+
 mel_status mel_wait_counter(const uint32_t* counter, uint32_t target, uint32_t timeout_us, void* stream) {
     if (!counter) return fail(MEL_ERR_INVALID_ARG, "mel_wait_counter: counter is null");
     clear_stale_error();

@@ -3,8 +3,12 @@
 // Included by env.hip inside namespace mel (it calls env_reset / env_store).  Three launches per refill:
 //   episode_draw_kernel    one thread per env: the env's own generator (numpy Generator(PCG64)) draws episode_seed, the
 //                          graph and the scripted set for each free ring slot, in order        core.py:372,378,395
+//                          (evaluation schedule, n_test > 0: the seed is read from the fixed list at the episode's list
+//                          position and only the scripted set comes from the generator        core.py:351-352,395)
 //   episode_fill_kernel    one wavefront per new episode: RandomState(episode_seed) (MT19937) draws movement seed, source,
-//                          interest density and the interested set; RandomState(movement_seed) fills the movement offsets;
+//                          interest density and the interested set (evaluation schedule: the graph first, and the density
+//                          from the list position instead of a draw, core.py:357-366); RandomState(movement_seed) fills the
+//                          movement offsets;
 //                          the graph is copied from the packed dataset; the scripted set loses the source (:213-215);
 //                          GraphEnv.reset + World.reset run into the snapshot batch    core.py:381-394,316-319,398-437
 //   episode_publish_kernel produced[b] += new_count[b]
@@ -100,18 +104,32 @@ __global__ __launch_bounds__(256) void episode_draw_kernel(StreamArgs a) {
     g.has32 = a.st.pcg_half[2 * (size_t)b], g.half = a.st.pcg_half[2 * (size_t)b + 1];
     const uint32_t graph_rng = (uint32_t)(a.graphs.n_graphs - 1);
     const int n = a.pool.n_nodes, k_scripted = a.st.n_scripted, words = MEL_SET_WORDS(n);
+    const int T = a.st.n_test;                                  // > 0: the evaluation schedule (core.py:348-370)
     for (int d = 0; d < a.discard; ++d) {                       // episodes the reference samples and throws away
-        (void)pcg64_bounded(g, 999999999u);
-        if (!a.st.fixed_graph) (void)pcg64_bounded(g, graph_rng);
+        if (T == 0) {
+            (void)pcg64_bounded(g, 999999999u);
+            if (!a.st.fixed_graph) (void)pcg64_bounded(g, graph_rng);
+        }
         if (k_scripted > 0) (void)pcg64_choice_set(g, n, k_scripted);
+    }
+    long long walked = 0;                                       // list entries this env has passed before episode 0
+    if (T > 0) {
+        walked = (long long)a.st.test_discarded[b] + a.discard;
+        a.st.test_discarded[b] = (int)walked;
     }
     const int cur = a.env.scalars[(size_t)b * MEL_ENV_SCALARS + MEL_S_EP_CURSOR];
     const int first = a.st.produced[b];
     int cnt = 0;
     while (cnt < a.max_new && first + cnt <= cur + K - 2) {
         const int slot = b * K + (first + cnt) % K;
-        a.st.draw_seed[slot] = pcg64_bounded(g, 999999999u);                                  // core.py:372
-        a.st.draw_graph[slot] = a.st.fixed_graph ? 0 : (int)pcg64_bounded(g, graph_rng);      // core.py:377-379
+        if (T > 0) {                                                                          // core.py:351-352
+            const int t = (int)(((long long)b * a.st.test_env_step + (walked + first + cnt) * a.st.test_episode_step) % T);
+            a.st.draw_seed[slot] = a.st.test_seeds[t];
+            a.st.draw_graph[slot] = t;                          // the fill draws the graph itself: it needs the position
+        } else {
+            a.st.draw_seed[slot] = pcg64_bounded(g, 999999999u);                                  // core.py:372
+            a.st.draw_graph[slot] = a.st.fixed_graph ? 0 : (int)pcg64_bounded(g, graph_rng);      // core.py:377-379
+        }
         if (k_scripted > 0) {                                                                 // core.py:395 (uniform branch)
             const NodeSet<2> set = pcg64_choice_set(g, n, k_scripted);
             for (int w = 0; w < words; ++w) a.st.draw_scripted[(size_t)slot * words + w] = set.w[w];
@@ -246,10 +264,16 @@ __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
         Mt m{key, 624};
         // ---- ep_rng = RandomState(episode_seed)                                                    core.py:373
         mt_seed(m, a.st.draw_seed[slot], lane);
-        const uint32_t movement_seed = mt_masked(m, 999999999u, lane);                              // :381
-        const int origin = (int)mt_masked(m, (uint32_t)(n - 1), lane);                              // :384
+        const int T = a.st.n_test;                           // wave-uniform: > 0 = the evaluation schedule
+        int g = a.st.draw_graph[slot];                       // training: the graph; evaluation: the list position
+        const int t = g;
+        if (T > 0) g = (int)mt_masked(m, (uint32_t)(a.graphs.n_graphs - 1), lane);                  // :357 (one graph: no draw)
+        const uint32_t movement_seed = mt_masked(m, 999999999u, lane);                              // :381 / :361
+        const int origin = (int)mt_masked(m, (uint32_t)(n - 1), lane);                              // :384 / :364
         double density = a.st.fixed_interest_density;
-        if (!a.st.has_density) {                                                                    // :385
+        if (T > 0) {                                         // :365-366 - the list index is read after it was bumped
+            density = (double)(((t + 1) % T) % 10 + 1) / 10.0;
+        } else if (!a.st.has_density) {                                                             // :385
             const uint32_t d0 = mt_next32(m, lane);
             const uint32_t d1 = mt_next32(m, lane);
             const double range = 1.0 - 0.1;
@@ -271,7 +295,6 @@ __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
         MEL_W_FOR(h) if (lane + 64 * h < k_int) mine |= ns_bit<W>(arr[h]);
         const NodeSet<W> interested = ns_wave_or(mine);
         // ---- the pool slot
-        const int g = a.st.draw_graph[slot];
         MEL_W_FOR(h) {
             if (lane + 64 * h < n) {
                 const size_t src = (size_t)g * n + lane + 64 * h, dst = (size_t)slot * n + lane + 64 * h;
@@ -331,6 +354,25 @@ __global__ __launch_bounds__(64) void wait_counter_kernel(const uint32_t* counte
     }
 }
 
+// The evaluation schedule's seed list (core.py:184-187): RandomState(17).randint(0, 1e9), n times.  One wavefront.
+__global__ __launch_bounds__(64) void episode_test_seeds_kernel(uint32_t* out, int n) {
+    __shared__ uint32_t key[624];
+    const int lane = threadIdx.x;
+    Mt m{key, 624};
+    mt_seed(m, 17u, lane);
+    for (int i = 0; i < n; ++i) {
+        const uint32_t v = mt_masked(m, 999999999u, lane);
+        if (lane == 0) out[i] = v;
+    }
+}
+
+static mel_status launch_episode_test_seeds(uint32_t* out, int32_t n, hipStream_t stream) {
+    if (!out || n < 1) return fail(MEL_ERR_INVALID_ARG, "mel_episode_test_seeds: out=%p n=%d", (void*)out, n);
+    clear_stale_error();
+    MEL_LAUNCH(episode_test_seeds_kernel, dim3(1), dim3(64), 0, stream, out, n);
+    return check_launch("episode_test_seeds");
+}
+
 static mel_status launch_episode_refill(const mel_episode_stream* st, const mel_graph_pool* graphs,
                                         const mel_episode_pool* pool, const mel_env_batch* env, int32_t max_new,
                                         int32_t discard, hipStream_t stream) {
@@ -343,7 +385,18 @@ static mel_status launch_episode_refill(const mel_episode_stream* st, const mel_
         return fail(MEL_ERR_INVALID_ARG, "graph pool of %d graphs x %d nodes for %d-node envs", graphs->n_graphs, graphs->n_nodes, env->n_nodes);
     if (st->fixed_graph && (graphs->n_graphs != 1 || env->dynamic_graph))
         return fail(MEL_ERR_UNSUPPORTED, "a fixed graph streams only when it is static (a moving fixed graph carries its positions over)");
-    if (env->is_testing) return fail(MEL_ERR_UNSUPPORTED, "the device sampler covers training mode (the evaluation schedule is a periodic table)");
+    if (env->is_testing && st->n_test == 0)
+        return fail(MEL_ERR_UNSUPPORTED, "an env in testing mode streams the evaluation schedule: set n_test and test_seeds");
+    if (st->n_test != 0) {
+        if (st->n_test < 0 || !env->is_testing)
+            return fail(MEL_ERR_INVALID_ARG, "n_test=%d: the evaluation schedule needs n_test > 0 and an env in testing mode", st->n_test);
+        if (st->fixed_graph) return fail(MEL_ERR_UNSUPPORTED, "testing mode draws its graph from the pool (core.py:355-359)");
+        if (!st->test_seeds || !st->test_discarded) return fail(MEL_ERR_INVALID_ARG, "n_test=%d needs test_seeds and test_discarded", st->n_test);
+        if (st->test_env_step < 0 || st->test_episode_step < 0)
+            return fail(MEL_ERR_INVALID_ARG, "test_env_step=%d test_episode_step=%d", st->test_env_step, st->test_episode_step);
+        if (discard > 0 && st->test_env_step != 0)
+            return fail(MEL_ERR_INVALID_ARG, "discard=%d with test_env_step=%d: only the reference's walk discards episodes", discard, st->test_env_step);
+    }
     // (n_scripted, not env->heuristic: a ratio without a heuristic is legal - scripted nodes then simply never act)
     if (st->n_scripted < 0 || st->n_scripted > env->n_nodes)
         return fail(MEL_ERR_INVALID_ARG, "n_scripted=%d for %d-node envs", st->n_scripted, env->n_nodes);

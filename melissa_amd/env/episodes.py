@@ -199,17 +199,27 @@ class EpisodeSampler:
     """The RNG protocol of World.reset (core.py:343-395), one instance per env.  Training mode draws the episode
     seed and the graph from the env's generator; testing mode (``is_testing``, core.py:182-187,348-370) walks a
     fixed list of ``num_test_episodes`` seeds derived from ``RandomState(17)`` in strict order, picks the graph
-    with the episode's own RNG from the (sorted) test pool and cycles the interest density through 0.1 .. 1.0."""
+    with the episode's own RNG from the (sorted) test pool and cycles the interest density through 0.1 .. 1.0.
+
+    ``test_env`` / ``test_env_step`` / ``test_episode_step`` place a testing-mode sampler on the list: its ``e``-th episode
+    sits at list position ``(test_env * test_env_step + e * test_episode_step) % num_test_episodes``.  The defaults
+    (0, 0, 1) are the reference's walk - the whole list from the top; ``test_env=b, test_env_step=1, test_episode_step=B``
+    gives env ``b`` of ``B`` the positions ``b, b + B, ...``, so that ``B`` envs share one pass over the list
+    (``mel_episode_refill`` draws the same positions on the device)."""
 
     def __init__(self, n: int, np_random: np.random.Generator, pool_size: int, fixed_graph: bool,
                  fixed_interest_density=None, is_testing: bool = False, num_test_episodes: int = 10,
-                 scripted_agents_ratio: float = 0.0):
+                 scripted_agents_ratio: float = 0.0, test_env_step: int = 0, test_episode_step: int = 1, test_env: int = 0):
         if not (0.0 <= scripted_agents_ratio <= 1.0):                                   # core.py:143-144
             raise ValueError("`scripted_agents_ratio` must be in [0.0, 1.0].")
         self.scripted_agents_ratio = float(scripted_agents_ratio)
         self.n, self.np_random, self.pool_size, self.fixed_graph = n, np_random, pool_size, fixed_graph
         self.fixed_interest_density = fixed_interest_density
         self.is_testing, self.num_test_episodes = bool(is_testing), int(num_test_episodes)
+        self.test_env, self.test_env_step, self.test_episode_step = int(test_env), int(test_env_step), int(test_episode_step)
+        if min(self.test_env, self.test_env_step, self.test_episode_step) < 0:
+            raise ValueError("test_env, test_env_step and test_episode_step must be >= 0")
+        self.test_episodes_sampled = 0
         self.test_episode_index = 0
         self.test_seeds_list = []
         if self.is_testing:
@@ -231,12 +241,18 @@ class EpisodeSampler:
             mask &= ~(1 << origin)
         return mask
 
+    def test_position(self, e: int) -> int:
+        """List position of this sampler's ``e``-th episode (discarded ones count)."""
+        return (self.test_env * self.test_env_step + int(e) * self.test_episode_step) % self.num_test_episodes
+
     def _sample_testing(self) -> Episode:
         n = self.n
         if not self.test_seeds_list:                                                    # core.py:349-350
             raise ValueError("No test seeds have been generated! Check num_test_episodes.")
-        episode_seed = self.test_seeds_list[self.test_episode_index]                    # :351
-        self.test_episode_index = (self.test_episode_index + 1) % self.num_test_episodes   # :352
+        position = self.test_position(self.test_episodes_sampled)
+        self.test_episodes_sampled += 1
+        episode_seed = self.test_seeds_list[position]                                   # :351
+        self.test_episode_index = (position + 1) % self.num_test_episodes               # :352
         ep_rng = np.random.RandomState(episode_seed)                                    # :353
         graph_index = int(ep_rng.randint(0, self.pool_size))      # :357 ep_rng.choice(test_graphs): same draw
         movement_seed = ep_rng.randint(0, 1e9)                                          # :361

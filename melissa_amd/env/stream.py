@@ -18,9 +18,15 @@ loops (``melissa_amd.collect``) take their episodes from an :class:`EpisodeStrea
   ``2 * period <= ring - 1`` no env can reach a slot that is being written or an episode that is not there yet; the env
   kernels check that anyway (``MEL_ENV_ERR_EPISODE_UNDERRUN``).
 
+:class:`TestEpisodeStream` is the same supply for the evaluation schedule (``is_testing``, core.py:182-187,348-370): the
+device reads the episode seed from the fixed list instead of drawing it, and the list can be walked whole by every env
+(the reference's order) or spread over the envs so that a batch passes over it once.  It is chosen explicitly
+(``make_supply(..., stream="test")``); an env in testing mode gets a static table otherwise, as before.
+
 :class:`StaticSupply` is the old behaviour for explicitly given tables (tests) and for the modes the device sampler
-does not cover (evaluation schedule, a moving fixed graph, training mode with EVERY node scripted): a fixed table; wrapping raises the same
-error flag unless the table is periodic by construction (the evaluation schedule is, core.py:351-352).
+does not cover (a moving fixed graph, training mode with EVERY node scripted) or is not asked for (the evaluation schedule):
+a fixed table; wrapping raises the same error flag unless the table is periodic by construction (the evaluation schedule
+is, core.py:351-352).
 """
 from __future__ import annotations
 
@@ -86,10 +92,16 @@ class EpisodeStream:
 
     kind = "device stream"
 
-    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
+    def _require_supported(self, venv):
         if not stream_supported(venv):
             raise ValueError("the device sampler covers training mode with fewer than all nodes scripted (and no moving "
-                             "fixed graph)")
+                             "fixed graph); the evaluation schedule streams from TestEpisodeStream")
+
+    def _configure(self, s, venv):
+        """Hook: further fields of the mel_episode_stream ``s`` before the first refill."""
+
+    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
+        self._require_supported(venv)
         if ring < 3:
             raise ValueError("ring must be >= 3")
         self.venv, self.ring = venv, int(ring)
@@ -137,6 +149,7 @@ class EpisodeStream:
         s.work, s.new_count = self.work.data_ptr(), self.new_count.data_ptr()
         s.n_scripted = self.n_scripted
         s.draw_scripted = self.draw_scripted.data_ptr() if self.n_scripted else None
+        self._configure(s, venv)
         self.struct = s
         self.side = torch.cuda.Stream(device=dev)
         self._ev_main = torch.cuda.Event()
@@ -214,14 +227,62 @@ class EpisodeStream:
                 "refills": self.refills}
 
 
-def make_supply(venv, seed, episodes=None, episodes_per_env: int = 8, stream: bool | None = None, ring: int = 16,
+class TestEpisodeStream(EpisodeStream):
+    """The evaluation schedule (``HipGraphVectorEnv(is_testing=True, num_test_episodes=T)``) from the device sampler: the
+    seed list is generated on the device (``mel_episode_test_seeds``), env b's e-th episode sits at the list position
+    ``venv.make_sampler(seed + b, env=b)`` gives it - the whole list from the top for every env, or positions
+    ``b, b + B, ...`` with ``spread_test_episodes``.  The envs' generators (seeded ``seed + b``) only draw the scripted
+    sets.  ``discard`` shifts the walk and is refused for a spread list."""
+
+    __test__ = False                   # (not a test class, whatever the name says to pytest)
+    kind = "device test stream"
+
+    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
+        if discard and venv._sampler_kw.get("test_env_step", 0):
+            raise ValueError(f"discard={discard}: only the reference's walk over the list discards episodes, a spread list "
+                             f"is played from its top")
+        super().__init__(venv, seed, ring=ring, discard=discard, period=period)
+
+    def _require_supported(self, venv):
+        kw = venv._sampler_kw
+        if not kw["is_testing"]:
+            raise ValueError("TestEpisodeStream draws the evaluation schedule: the env must be built with is_testing=True")
+        if kw["scripted_agents_ratio"] >= 1.0:
+            raise ValueError("the device sampler takes the source out of the scripted set: every node scripted "
+                             "(scripted_agents_ratio 1.0) needs a host-drawn table")
+        if kw["num_test_episodes"] < 1:
+            raise ValueError("No test seeds have been generated! Check num_test_episodes.")      # core.py:349-350
+
+    def _configure(self, s, venv):
+        kw, dev = venv._sampler_kw, venv.device
+        s.n_test = int(kw["num_test_episodes"])
+        s.test_env_step, s.test_episode_step = int(kw.get("test_env_step", 0)), int(kw.get("test_episode_step", 1))
+        self.test_seeds = torch.zeros(s.n_test, dtype=torch.int32, device=dev)
+        self.test_discarded = torch.zeros(venv.env_num, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.mel_episode_test_seeds(self.test_seeds.data_ptr(), s.n_test, _lib.current_stream_ptr(dev)),
+                   "mel_episode_test_seeds")
+        s.test_seeds, s.test_discarded = self.test_seeds.data_ptr(), self.test_discarded.data_ptr()
+
+    def describe(self) -> dict:
+        out = super().describe()
+        out.update(mode="device test stream", test_episodes=int(self.struct.n_test),
+                   walk=(int(self.struct.test_env_step), int(self.struct.test_episode_step)))
+        return out
+
+
+def make_supply(venv, seed, episodes=None, episodes_per_env: int = 8, stream: "bool | str | None" = None, ring: int = 16,
                 discard: int = 0, reset_snapshots: bool = True):
     """``episodes`` = (packed, table): that static table.  Otherwise a device stream where the sampler covers the env's
     mode (``stream`` None / True) or a host-drawn table of ``episodes_per_env`` episodes (``stream`` False, or a mode
-    the device sampler does not cover)."""
+    the device sampler does not cover).  ``stream="test"``: the evaluation schedule from the device
+    (:class:`TestEpisodeStream`); an env in testing mode gets a host-drawn table unless asked for this."""
     from ..collect import sample_episode_table
     if episodes is not None:
         return StaticSupply(venv, episodes[0], episodes[1], reset_snapshots)
+    if isinstance(stream, str):
+        if stream != "test":
+            raise ValueError(f"stream={stream!r}: None, True, False or 'test'")
+        return TestEpisodeStream(venv, seed, ring=ring, discard=discard)
     if stream is None:
         stream = stream_supported(venv)
     if stream:

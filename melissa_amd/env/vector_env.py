@@ -183,7 +183,7 @@ class HipGraphVectorEnv:
                  dynamic_graph: bool = False, local_ratio=None, device="cuda", max_moves: int = 64,
                  seed=None, fixed_interest_density=None, construct_like_reference: "bool | int" = True,
                  is_testing: bool = False, num_test_episodes: int = 10, scripted_agents_ratio: float = 0.0,
-                 heuristic: str | None = None):
+                 heuristic: str | None = None, spread_test_episodes: bool = False):
         """``graph`` fixes one graph for every episode (GraphEnv(graph=...)); ``graph_pool`` is a list of
         ``Graph`` standing for the ``graph_topologies/training_N/*`` files.  ``seed`` seeds env k's
         generator with ``seed + k`` (tianshou ``BaseVectorEnv.seed``).  ``construct_like_reference``
@@ -193,7 +193,11 @@ class HipGraphVectorEnv:
         tianshou PettingZooEnv.__init__ -> env.reset()), ``2`` for a bare ``GraphEnv`` (what the golden traces
         drive), ``False`` for none.  ``is_testing``: the
         reference's evaluation schedule (GraphEnv(is_testing=True, num_test_episodes=...), core.py:182-187,348-370);
-        ``graph_pool`` then stands for the sorted ``graph_topologies/testing_N/*`` files."""
+        ``graph_pool`` then stands for the sorted ``graph_topologies/testing_N/*`` files.  ``spread_test_episodes`` (testing
+        mode only): env ``b`` of ``B`` plays list positions ``b, b + B, ...`` instead of the whole list from the top, so that
+        the batch passes over the list once (``EpisodeSampler``'s ``test_env_step=1, test_episode_step=B``)."""
+        if spread_test_episodes and not is_testing:
+            raise ValueError("spread_test_episodes spreads the evaluation schedule: it needs is_testing")
         _lib.check_n_nodes(number_of_agents, "HipGraphVectorEnv")
         if is_testing and graph is not None:
             raise ValueError("testing mode draws its graph from graph_pool (core.py:355-359)")
@@ -218,7 +222,9 @@ class HipGraphVectorEnv:
         seeds = [None] * self.env_num if seed is None else [seed + k for k in range(self.env_num)]
         self._sampler_kw = dict(fixed_interest_density=fixed_interest_density, is_testing=is_testing,
                                 num_test_episodes=num_test_episodes, scripted_agents_ratio=scripted_agents_ratio)
-        self.samplers = [self.make_sampler(s) for s in seeds]
+        if spread_test_episodes:
+            self._sampler_kw.update(test_env_step=1, test_episode_step=self.env_num)
+        self.samplers = [self.make_sampler(s, env=k) for k, s in enumerate(seeds)]
         # device state
         nbytes = int(self.lib.mel_env_state_bytes(self.env_num, self.n))
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -258,11 +264,12 @@ class HipGraphVectorEnv:
             self.log_cursor.zero_()
         return out
 
-    def make_sampler(self, seed) -> EpisodeSampler:
+    def make_sampler(self, seed, env: int = 0) -> EpisodeSampler:
         """An episode sampler with this env's settings (graph pool size, evaluation schedule, scripted ratio, ...)
-        and its own generator seeded ``seed`` - what the device-resident loops pre-draw their episode pools with."""
+        and its own generator seeded ``seed`` - what the device-resident loops pre-draw their episode pools with.
+        ``env``: which env of the batch it stands for (only a spread evaluation schedule depends on it)."""
         return EpisodeSampler(self.n, np.random.Generator(np.random.PCG64(np.random.SeedSequence(seed))),
-                              len(self.graphs), self.fixed_graph, **self._sampler_kw)
+                              len(self.graphs), self.fixed_graph, test_env=env, **self._sampler_kw)
 
     # ------------------------------------------------------------------ plumbing
     def __len__(self):

@@ -91,6 +91,31 @@ def _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scri
     return out
 
 
+def _evaluate_spread(policy, n_nodes, test_num, test_envs, eps_test, seed, device, heuristic, scripted_agents_ratio) -> dict:
+    """The same ``test_num`` episodes as :func:`_evaluate` - same env settings, same list of test seeds, same graph pool - played
+    by ``test_envs`` envs at once: env b takes list positions ``b, b + test_envs, ...``, the schedule is drawn on the device and
+    the rounds replay from a HIP graph (:func:`melissa_amd.collect.evaluate_spread`).  Means are taken in list-position order.
+    With ``eps_test`` 0 the episodes are the ones :func:`_evaluate` plays; with exploration the random draws differ (they are
+    indexed by env and round)."""
+    import numpy as np
+    from . import _lib
+    from .collect import evaluate_spread
+    from .env import HipGraphVectorEnv, synthetic_graph_pool
+    venv = HipGraphVectorEnv(test_envs, n_nodes, graph_pool=synthetic_graph_pool(n_nodes, 16, first_seed=0), dynamic_graph=True,
+                             device=device, max_moves=64, seed=seed, construct_like_reference=False, is_testing=True,
+                             num_test_episodes=test_num, scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic,
+                             spread_test_episodes=True)
+    was_training = policy.model.training
+    policy.model.eval()
+    try:
+        res, _positions = evaluate_spread(policy, venv, test_num, eps=eps_test, seed=seed)
+    finally:
+        policy.model.train(was_training)
+    out = dict(rew=float(np.mean(res.returns)), len=float(np.mean(res.lens)), episodes=int(test_num))
+    out.update({k: float(np.mean(res.episode_info[k])) for k in _lib.LOGGER_KEYS})
+    return out
+
+
 def _agreed_decisions(loop, world, device) -> int:
     """The decision count every rank uses for the run's env steps: the smallest rank's (a host read: synchronises)."""
     from . import parallel
@@ -258,7 +283,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
           heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
-          update_per_step=None, step_per_collect=10, buffer_size=None):
+          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -284,7 +309,12 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     updates are one HIP launch each (``fused_td``, :mod:`melissa_amd.td`).  An iteration then collects ``step_per_collect`` env
     steps (``--step-per-collect``, common.py:34: :func:`rounds_per_collect` rounds instead of ``rounds_per_update``).
     ``buffer_size``: the reference's ``--buffer-size`` (transitions in all; :func:`replay_rounds_for` rounds per env instead of
-    ``replay_rounds``)."""
+    ``replay_rounds``).
+    ``test_envs`` (epoch mode): 1 evaluates with one env, a host-drawn episode table and eager rounds; more evaluates with
+    ``min(test_envs, test_num)`` envs that share one pass over the list of test seeds, drawn on the device and replayed from a
+    HIP graph (:func:`_evaluate_spread`).  The epoch records carry the number used as ``test_envs``."""
+    if int(test_envs) < 1:
+        raise ValueError(f"test_envs={test_envs} must be >= 1")
     if update_per_step is not None:
         if epoch is None:
             raise ValueError("update_per_step paces the updates of the epoch mode: it needs epoch")
@@ -381,8 +411,18 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         torch.cuda.synchronize(device)
         dt = time.perf_counter() - t0
     else:
+        n_test_envs = min(int(test_envs), int(test_num))
+
         def evaluate():
-            return _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scripted_agents_ratio) if rank == 0 else None
+            if rank != 0:
+                return None
+            if n_test_envs > 1:
+                stats = _evaluate_spread(policy, n_nodes, test_num, n_test_envs, eps_test, seed, device, heuristic,
+                                         scripted_agents_ratio)
+            else:
+                stats = _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scripted_agents_ratio)
+            stats["test_envs"] = n_test_envs
+            return stats
         weights_dir = os.path.join(logdir, model, "weights")
         name = model_name if model_name is not None else default_model_name()
         # (epoch mode captures the update AFTER the first evaluation: `param_checksum_start`, that evaluation and the first
@@ -458,6 +498,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--exploration-fraction", type=float, default=0.6)
     ap.add_argument("--eps-test", type=float, default=0.001)
     ap.add_argument("--test-num", type=int, default=100)
+    ap.add_argument("--test-envs", type=int, default=1,
+                    help="envs of an evaluation: 1 plays the --test-num episodes one after another; more share them out, draw "
+                         "them on the device and replay the rounds from a HIP graph")
     ap.add_argument("--logdir", type=str, default="log")
     ap.add_argument("--model-name", type=str, default=default_model_name())
     ap.add_argument("--resume-path", type=str, default=None)
@@ -479,7 +522,8 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 eps_train=a.eps_train, eps_train_final=a.eps_train_final, exploration_fraction=a.exploration_fraction,
                 eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
                 seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq,
-                update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size)
+                update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size,
+                test_envs=a.test_envs)
 
 
 def parse_args(argv=None) -> argparse.Namespace:

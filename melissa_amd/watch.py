@@ -2,7 +2,12 @@
 run test episodes on evaluation envs, report the episodes' statistics).
 
     python -m melissa_amd.watch --model l_dgn --nodes 20 --envs 1 --episodes 10 [--load policy.pth]
-                                [--heuristic mpr --scripted-agents-ratio 0.5]
+                                [--heuristic mpr --scripted-agents-ratio 0.5] [--envs 16 --spread]
+
+``--envs E`` alone makes every env walk the list of test seeds from the top (the reference's order, core.py:351-352): the
+``--episodes`` episodes reported are the first ``ceil(episodes / E)`` list positions, ``E`` times over.  ``--spread`` shares
+the list out instead - env b plays positions ``b, b + E, ...``, each of the ``--episodes`` positions exactly once - drawn on
+the device and replayed from a HIP graph (:func:`melissa_amd.collect.evaluate_spread`).
 
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
 ``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by ``python -m melissa_amd.train --epoch ...``
@@ -18,14 +23,14 @@ import json
 
 import torch
 
-from .collect import Collector
+from .collect import Collector, evaluate_spread
 from .env import HipGraphVectorEnv, synthetic_graph_pool
 from .policy import DQNPolicy
 from .train import N_DGN_NETWORK, build_network
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
-          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0):
+          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False):
     torch.manual_seed(seed)
     net = build_network(model, n_nodes, device)
     policy = DQNPolicy(net, target_update_freq=1)
@@ -34,19 +39,24 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     net.eval()
     net.set_feature_dtype(feature_dtype)
     pool = graph_pool if graph_pool is not None else synthetic_graph_pool(n_nodes, 16, first_seed=0)
+    if spread:
+        envs = min(envs, episodes)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=pool, dynamic_graph=dynamic_graph, device=device, max_moves=64,
                              seed=seed, construct_like_reference=False, is_testing=True, num_test_episodes=episodes,
-                             scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic)
-    per_env = -(-episodes // envs) + 2
-    col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64)
-    out = col.collect(n_episode=episodes)
+                             scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic, spread_test_episodes=spread)
+    if spread:
+        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed)
+    else:
+        per_env = -(-episodes // envs) + 2
+        col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64)
+        out = col.collect(n_episode=episodes)
     # the scalars of the collect result (counts, speed, mean return / length, mean of every logger_stats key) as a plain dict
     keys = ["n/ep", "n/st", "collect_time", "collect_speed"] + (["rew", "len"] if out.returns_stat is not None else []) \
         + list(out.info.stats)
     return {k: out[k] for k in keys}
 
 
-def main(argv=None):
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     # (the three N-DGN scripts train these networks under their own names: a checkpoint of theirs loads into the same classes)
     ap.add_argument("--model", default="l_dgn", choices=["l_dgn", "hl_dgn", "dgn_r", *N_DGN_NETWORK])
@@ -59,9 +69,16 @@ def main(argv=None):
                     help="heuristic the scripted agents run (common.py:67)")
     ap.add_argument("--scripted-agents-ratio", type=float, default=0.0,
                     help="fraction of the nodes that are scripted agents (common.py:69)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--spread", action="store_true", default=False,
+                    help="share the --episodes test seeds out over the --envs envs (each played once) instead of every env "
+                         "walking the list from the top")
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
     print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype, heuristic=a.heuristic,
-                           scripted_agents_ratio=a.scripted_agents_ratio)))
+                           scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread)))
 
 
 if __name__ == "__main__":
