@@ -718,7 +718,10 @@ mel_status mel_replay_sample(const mel_round_replay* replay, int64_t n_envs, int
  *   rec_sum   double [B * K]    scratch: per-record sums
  *   prefix    double [B * K + 1] scratch: their exclusive prefix sums, prefix[B * K] = total
  *   seen      int32  [B]        cursor[b] at the last sample (start: 0): records written since then are initialised lazily to
- *                               max_prio^alpha by the next sample - upstream's add(), without touching mel_env_round
+ *                               max_prio^alpha by the next sample - upstream's add(), without touching mel_env_round.
+ *                               Written = ring slots seen .. cursor - 1 (mod K); all of them once cursor - seen >= K, or < 0 (the
+ *                               cursor went back: the ring was reset).  A slot at or beyond min(cursor, K) holds no record: it is
+ *                               never initialised from its (stale) acted set, and every sample sets its priorities to 0
  *   max_prio / min_prio float scalars: largest / smallest raw p = |td| + eps written back so far (start: 1.0)
  * alpha, beta >= 0; weight_norm != 0 divides the importance weights by their maximum over the batch (upstream's default). */
 typedef struct mel_replay_priority {

@@ -7,7 +7,8 @@
 // yet filled, so the buffer order of upstream's prefix sums is this array's memory order.  Three launches:
 //   refresh     one wavefront per record: records written since the last sample get max_prio^alpha (upstream's add(): max_prio
 //               only changes in the write-back, and every write-back is preceded by a sample, so a record first seen by a sample
-//               gets the max_prio it would have been added with); every record's priorities are summed in agent order into f64.
+//               gets the max_prio it would have been added with), slots at or beyond min(cursor, K) get 0; every record's
+//               priorities are summed in agent order into f64.
 //   sample      one workgroup: f64 exclusive scan of the record sums in fixed order, per sample target = u * total, binary
 //               search for the record, a walk over its N priorities for the agent, importance weights
 //               (p^alpha / min_prio)^-beta [/ max over the batch].
@@ -37,7 +38,12 @@ __global__ __launch_bounds__(256) void replay_prio_refresh_kernel(mel_round_repl
     }
     float* p = pr.prio + (size_t)rec * n;
     float v0 = 0.f, v1 = 0.f;                              // agents lane and lane + 64
-    if (fresh) {
+    if (k >= min(rp.cursor[e], K)) {
+        // no record yet: never fresh (a cursor that went back makes the whole env "written", and acted holds stale sets here), and
+        // never priority mass - the sample kernel has no filled check of its own
+        if (lane < n) p[lane] = 0.f;
+        if (lane + 64 < n) p[lane + 64] = 0.f;
+    } else if (fresh) {
         const float init = powf(*pr.max_prio, (float)pr.alpha);
         const unsigned long long m0 = rp.acted[(size_t)rec * W];
         v0 = (m0 >> lane) & 1 ? init : 0.f;

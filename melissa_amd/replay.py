@@ -270,14 +270,16 @@ class PrioritizedRoundReplay(RoundReplay):
 
     def refresh(self) -> None:
         """Host form of the lazy initialisation (the device does it inside ``sample``): records written since the last sample get
-        ``max_prio ** alpha`` for their acting agents, 0 elsewhere."""
+        ``max_prio ** alpha`` for their acting agents, 0 elsewhere.  A slot at or beyond ``min(cursor, K)`` holds no record: it is
+        never fresh, whatever ``seen`` says (a cursor that went back marks the whole env written), and its priorities are 0."""
         cur, seen = self.cursor.long(), self.seen.long()
         written = cur - seen
         d = (torch.arange(self.K, device=cur.device)[None, :] - (seen % self.K)[:, None]) % self.K           # [B, K]
         fresh = (written[:, None] >= self.K) | (written[:, None] < 0) | (d < written[:, None])
         init = torch.pow(self.max_prio, self.alpha)                                                        # float32, like powf
-        new = torch.where(self._members(self.acted), init, torch.zeros((), device=cur.device))
-        self.prio.copy_(torch.where(fresh[:, :, None], new, self.prio))
+        zero = torch.zeros((), device=cur.device)
+        new = torch.where(self._members(self.acted), init, zero)
+        self.prio.copy_(torch.where(self._valid_slots()[:, :, None], torch.where(fresh[:, :, None], new, self.prio), zero))
         self.seen.copy_(self.cursor)
 
     def sample(self, batch_size: int, n_step: int, gamma: float, generator: torch.Generator | None = None):
