@@ -165,6 +165,12 @@ mel_status mel_prepare_weights(const mel_weights* w, void* prepared, size_t byte
  * for bf16 / split, needs mel_weights.prepared. */
 size_t mel_feature_tables_bytes(const mel_weights* w, int32_t n_nodes);
 mel_status mel_prepare_feature_tables(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, void* stream);
+/* The same table, same buffer layout and same bits, by the ONE launch in which a forward evaluates it beside its row lists
+ * (a workgroup makes the encoder rows of 32 tuples, keeps them in LDS and runs 256 conv1 columns on them): the table work
+ * items alone, no lists.  MEL_ERR_UNSUPPORTED where the forward keeps the two-launch form: anything but GATv2 L-DGN at
+ * MEL_PREC_F32 / MEL_PREC_F32_AUTO with hidden = 128.  (MEL_NO_FUSED_TABLE in the environment, read once per process, makes
+ * the FORWARD take the two-launch form for A/B runs; this entry point does not look at it.) */
+mel_status mel_feature_tables_fused(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, void* stream);
 
 /* Bytes of scratch the forward needs for `bs` observation rows of `n_nodes`-node graphs. */
 size_t mel_workspace_bytes(const mel_weights* w, int64_t bs, int32_t n_nodes);

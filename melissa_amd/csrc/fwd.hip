@@ -26,10 +26,19 @@ Profiler* current_profiler() { return g_prof; }
 // The row lists of a forward and the encoder rows of its node-feature table in ONE launch: the first `gemm_blocks`
 // workgroups are 64 x 64 tiles of the (feature-domain) encoder GEMM, the rest run plan_lists.  The two are independent (the
 // table depends on the weights only) and each is a latency-bound launch of a few hundred workgroups on its own.
-template <int W>
-__global__ __launch_bounds__(256, 2) void plan_enc_kernel(PlanListsArgs pa, GemmBatch batch, int gemm_blocks) {
-    if ((int)blockIdx.x < gemm_blocks) gemm_f32_tile<2, 2, 1, 1, GEMM_MODE_ENC>(batch, (int)blockIdx.x);
-    else plan_lists_body<W>(pa, (int)blockIdx.x - gemm_blocks);
+// FUSED: the first workgroups are work items of the WHOLE table instead (table_fused_tile, gemm_table.hpp: encoder rows and
+// conv1's projections of them), and no launch for the table follows.
+template <int W, bool FUSED = false>
+__global__ __launch_bounds__(256, 2) void plan_enc_kernel(PlanListsArgs pa, std::conditional_t<FUSED, TableArgs, GemmBatch> work,
+                                                          int gemm_blocks) {
+    if constexpr (FUSED) {
+        __shared__ __attribute__((aligned(16))) float lds[TBL_LDS_FLOATS];
+        if ((int)blockIdx.x < gemm_blocks) table_fused_tile(work, (int)blockIdx.x, lds);
+        else plan_lists_body<W>(pa, (int)blockIdx.x - gemm_blocks);
+    } else {
+        if ((int)blockIdx.x < gemm_blocks) gemm_f32_tile<2, 2, 1, 1, GEMM_MODE_ENC>(work, (int)blockIdx.x);
+        else plan_lists_body<W>(pa, (int)blockIdx.x - gemm_blocks);
+    }
 }
 
 // HL-DGN's counterpart: its tuple ids (feature_ids) beside the encoder rows of the table, one launch instead of two
@@ -467,6 +476,28 @@ static FeatureTables carve_tables(const mel_weights* w, int n, void* buf, size_t
     if (bytes) *bytes = c.off;
     return t;
 }
+// The shapes table_fused_tile is built for (gemm_table.hpp): GATv2 L-DGN on the exact-fp32 instruction - MEL_PREC_F32, and
+// MEL_PREC_F32_AUTO, whose table launches are far too small for the split kernels.  Everything else (the bf16 feature path,
+// MEL_PREC_F32_SPLIT, DGN-R's three source-side matrices, HL-DGN) keeps the two-launch form.
+static bool table_fuses(const mel_weights* w) {
+    const int hc = w->conv1.heads * w->conv1.channels, K0 = w->encoder.layer[0].out_dim;
+    return w->model == MEL_MODEL_LDGN && w->conv1.kind != MEL_CONV_TRANSFORMER &&
+           (w->precision == MEL_PREC_F32 || w->precision == MEL_PREC_F32_AUTO) && w->in_dim == 5 && w->encoder.n_layers == 2 &&
+           K0 == TBL_HIDDEN && w->encoder.layer[1].out_dim == TBL_HIDDEN &&
+           w->conv1.lin_l.in_dim == TBL_HIDDEN && hc % 32 == 0 && (2 * hc) % TBL_BN == 0;
+}
+static TableArgs fused_table_args(const mel_weights* w, const ProjWeights& pw, int n, const FeatureTables& t) {
+    const int hc = w->conv1.heads * w->conv1.channels;
+    TableArgs a;
+    a.T = n * FEATURE_TUPLES_PER_DEGREE, a.in_dim = w->in_dim;
+    a.enc_w = w->encoder.layer[0].weight, a.enc_b = w->encoder.layer[0].bias;
+    a.W1 = pw.enc1, a.b1 = w->encoder.layer[1].bias;
+    a.Wl = pw.c1l, a.Wr = pw.c1r, a.bl = w->conv1.lin_l.bias, a.br = w->conv1.lin_r.bias;
+    a.split_n = hc, a.N = 2 * hc;
+    a.h0 = t.h0, a.xl = t.xl, a.xr = t.xr;
+    return a;
+}
+
 static mel_status run_feature_tables(const mel_weights* w, const ProjWeights& pw, int n, const FeatureTables& t, hipStream_t s,
                                      bool encoder_done = false) {
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
@@ -539,7 +570,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     // Node-feature table (plan_masks.hpp): worth it when the row lists are much longer than the N * 40 tuples
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
     const bool table = (w->flags & MEL_FWD_INTEGER_FEATURES) && w->in_dim == 5 && hint1 + hint2 >= 2L * T;
-    bool fused_enc = false;
+    bool fused_enc = false, fused_table = false;
     // conv2's projections, planned HERE: on gemm_planes_kernel (both operands as bf16 planes in blocks, gemm_split.hpp) the
     // conv1 attention stores h1 already split, as that kernel's A operand.  (h1 rows are masked by the decision-maker flag,
     // l_dgn.py:128: the conv1 attention applies it as it stores them.)
@@ -582,9 +613,17 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         // only) are independent - ONE launch runs both (plan_enc_kernel) instead of two latency-bound ones back to back
         // (bf16 feature path: the same fp32 tile on the fp32 encoder weights, its rows stored as bf16 - the bf16 ENC launch of the
         //  2 000 tuples alone took 15 us)
+        // ... and where table_fused_tile fits, the same workgroups run conv1's projections of their encoder rows: the whole
+        // table inside this launch
         fused_enc = table && !sp && !(w->tables && w->tables_nodes == n);
+        fused_table = fused_enc && table_fuses(w) && !gemm_tuning().no_fused_table;
         const PlanListsArgs pa{obs, (int)bs, n, obs_stride, node_cols, L.plan, row_offsets_out, tconv ? 0 : 1, inline_scan, table ? T : 0};
-        if (fused_enc) {
+        if (fused_table) {
+            const TableArgs ta = fused_table_args(w, pw, n, FeatureTables{L.h0, L.xl1, L.xr1});
+            const int tiles = table_items(ta);
+            if (n > 64) MEL_LAUNCH((plan_enc_kernel<2, true>), dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, ta, tiles);
+            else MEL_LAUNCH((plan_enc_kernel<1, true>), dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, ta, tiles);
+        } else if (fused_enc) {
             GemmArgs g;
             g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
             g.W = bf ? w->encoder.layer[1].weight : pw.enc1, g.bias = w->encoder.layer[1].bias, g.y_bf16 = bf;
@@ -618,6 +657,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     FeatureTables ft{L.h0, L.xl1, L.xr1};
     if (table) {
         if (w->tables && w->tables_nodes == n) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
+        else if (fused_table) {}        // the plan launch made all three
         else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc)) return st;
     }
     {   // conv1.lin_l on the U2 rows + conv1.lin_r on the U1 rows, one grouped launch
@@ -703,6 +743,15 @@ void mel_debug_gemm_prof(unsigned long long* out8) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), z, sizeof(z));
 }
 #endif
+#ifdef MEL_TABLE_PROF
+// tuning builds only: read and reset the table work items' cycle counters (tools/table_prof.py)
+void mel_debug_table_prof(unsigned long long* out8) {
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_table_prof), 8 * sizeof(unsigned long long));
+    unsigned long long z[8] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_table_prof), z, sizeof(z));
+}
+#endif
 #ifdef MEL_SPLIT_PROF
 void mel_debug_split_prof(unsigned long long* out16) {
     (void)hipDeviceSynchronize();
@@ -766,6 +815,23 @@ mel_status mel_prepare_feature_tables(const mel_weights* w, int32_t n_nodes, voi
     FwdLayout none{};
     if (mel_status st = resolve_projections(w, none, pw, pw_alt, s)) return st;
     return run_feature_tables(w, pw, n_nodes, carve_tables(w, n_nodes, tables, nullptr), s);
+}
+
+mel_status mel_feature_tables_fused(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, void* stream) {
+    if (mel_status st = validate(w, w ? w->model : 0, 1, n_nodes, n_nodes * ((w ? w->in_dim : 5) + 3), false)) return st;
+    if (!table_fuses(w)) return fail(MEL_ERR_UNSUPPORTED, "the one-launch table is built for GATv2 L-DGN at f32 / f32-auto precision, hidden = %d", TBL_HIDDEN);
+    const size_t need = mel_feature_tables_bytes(w, n_nodes);
+    if (!tables || bytes < need) return fail(MEL_ERR_WORKSPACE, "feature-table buffer %zu < %zu bytes", bytes, need);
+    if (w->precision != MEL_PREC_F32 && !w->prepared)
+        return fail(MEL_ERR_INVALID_ARG, "bf16 / split precision: prepare the weights first (mel_prepare_weights)");
+    clear_stale_error();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ProjWeights pw, pw_alt;
+    FwdLayout none{};
+    if (mel_status st = resolve_projections(w, none, pw, pw_alt, s)) return st;
+    const TableArgs ta = fused_table_args(w, pw, n_nodes, carve_tables(w, n_nodes, tables, nullptr));
+    MEL_LAUNCH(table_fused_kernel, dim3(table_items(ta)), dim3(256), 0, s, ta);
+    return check_launch("feature tables, one launch");
 }
 
 mel_status mel_prepare_weights(const mel_weights* w, void* prepared, size_t bytes, void* stream) {

@@ -120,15 +120,17 @@ struct AChunk {
 // node list), or - feat_domain - decoded from the row index itself: the features are small integers (degree, messages
 // sent, last action, interested, has message; graph.py:261-269), so the encoder and conv1 projections can be evaluated
 // once per distinct TUPLE instead of once per node row (node-feature table, plan_masks.hpp).
-__device__ __forceinline__ void enc_features(const GemmArgs& g, int row, float x[8]) {
+__device__ __forceinline__ void tuple_features(int row, float x[8]) {
 #pragma unroll
     for (int f = 0; f < 8; ++f) x[f] = 0.f;
-    if (g.feat_domain) {
-        const int deg = row / 40, rem = row - deg * 40;               // tuple id = degree * 40 + messages * 8 + flags
-        x[0] = (float)deg, x[1] = (float)(rem >> 3), x[2] = (float)((rem >> 2) & 1);
-        x[3] = (float)((rem >> 1) & 1), x[4] = (float)(rem & 1);
-        return;
-    }
+    const int deg = row / 40, rem = row - deg * 40;                   // tuple id = degree * 40 + messages * 8 + flags
+    x[0] = (float)deg, x[1] = (float)(rem >> 3), x[2] = (float)((rem >> 2) & 1);
+    x[3] = (float)((rem >> 1) & 1), x[4] = (float)(rem & 1);
+}
+__device__ __forceinline__ void enc_features(const GemmArgs& g, int row, float x[8]) {
+    if (g.feat_domain) return tuple_features(row, x);
+#pragma unroll
+    for (int f = 0; f < 8; ++f) x[f] = 0.f;
     const int id = g.nid ? g.nid[row] : row;
     const int b = id / g.n_nodes, node = id - b * g.n_nodes;
     const float* src = g.obs + (size_t)b * g.obs_width + node * g.node_cols + 2;
