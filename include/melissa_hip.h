@@ -412,6 +412,9 @@ mel_status mel_exploration_schedule(const int32_t* decisions, int32_t stride, in
  * mel_env_state_bytes() gives the size, mel_env_bind() carves the pointer table.
  * ------------------------------------------------------------------------------------------------ */
 #define MEL_ENV_LOGGER_STATS  10   /* graph.py:167-177, in dict order                            */
+/* doubles of one env's per-step logger_stats accumulator (mel_env_batch.step_stats): the sample count, then per key
+ * the running mean, M2 (sum of squared deviations from the mean), min and max */
+#define MEL_ENV_STEP_STATS_DOUBLES (1 + 4 * MEL_ENV_LOGGER_STATS)
 
 /* node_sets[b][k] */
 #define MEL_SET_HAS_MESSAGE    0   /* State.has_message                        core.py:18        */
@@ -489,6 +492,19 @@ typedef struct mel_env_batch {
     uint64_t* plan_u1;         /* [B]   */
     uint64_t* plan_u2;         /* [B]   */
     int32_t*  plan_cnt;        /* [3*B] */
+    /* Optional per-step logger_stats pool (caller-owned, zero-initialised; NULL = off; kept across mel_env_bind like the
+     * log_* pointers): [B, MEL_ENV_STEP_STATS_DOUBLES].  The reference's collectors pool the `logger_stats` of EVERY env.step
+     * of every env (multi_agent_collector.py:276,316-322).  With the pool on, every AEC sub-step mel_env_round replays
+     * (live, dead and episode-ending steps alike, the fast-forwarded ones included) and every mel_env_step call with an
+     * output block adds one sample to its env's accumulator: the ten values STORED in infos[agent_selection] after the
+     * step (what env.last() returns, stale or not), nothing when that slot holds no logger_stats (MEL_SEL_INFO_VALID
+     * clear, or no selection).  Resets, mel_env_observe and the `first` launch of mel_env_round add nothing.  Per env:
+     * [0] sample count, then per key k [1 + 4k ..]: mean, M2, min, max, merged by the Chan / Welford rule (n = na + nb,
+     * d = mb - ma, mean = ma + d * nb / n, M2 = M2a + M2b + d * d * na * nb / n) by the one wavefront that owns the env.
+     * Count-gated: with a count of 0 the other 40 values mean nothing (an all-zero buffer is an empty pool); the first
+     * sample sets mean = min = max = value, M2 = 0.  Read with mel_env_step_stats.  (It stands with the other caller-owned
+     * pointers, in front of received_from, which stays the last field of the struct as it is the last one carved.) */
+    double*   step_stats;
     /* State.received_from (core.py:22,276-278) as node sets: node i's set holds every node it has received the message
      * from this episode.  Carved by mel_env_bind behind every other field; read and written only when heuristic ==
      * MEL_HEURISTIC_MPR (rule core.py:236-243 is the only reader).  Empty at each reset, then set by the reset's own
@@ -829,6 +845,14 @@ mel_status mel_env_round(mel_env_batch* env, const mel_episode_pool* pool, const
                          const int32_t* row_offsets, uint64_t* live, const int32_t* episode_table,
                          int32_t table_stride, int32_t first, uint32_t* round_counter,
                          const mel_round_replay* replay, void* stream);
+
+/* Reads the per-step logger_stats pool (mel_env_batch.step_stats): one workgroup merges the B per-env accumulators in a
+ * fixed order (thread t folds envs t, t + 256, ... in index order, then a fixed pairwise tree), so the result is the
+ * same from run to run.  out: device double [1 + 4 * MEL_ENV_LOGGER_STATS] = the sample count, then per key mean, std, max,
+ * min - std = sqrt(M2 / n), the population std of SequenceSummaryStats.from_sequence (collector.py:14-30).  No sample:
+ * count 0 and zeros.  reset != 0 also empties every env's accumulator in the same launch (all 41 doubles to zero: the
+ * count gates the rest).  MEL_ERR_INVALID_ARG: env or out NULL, an unbound batch, step_stats == NULL. */
+mel_status mel_env_step_stats(const mel_env_batch* env, double* out, int32_t reset, void* stream);
 
 /* last() only (mutates is_new_round exactly like GraphEnv.observe, graph.py:205-211). */
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n,

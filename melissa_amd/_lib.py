@@ -29,6 +29,7 @@ CONV_GATV2, CONV_TRANSFORMER = 0, 1
 AGG = {"max": 0, "mean": 1, "add": 2}
 OK, ERR_INVALID_ARG, ERR_SHAPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_LAUNCH = 0, -1, -2, -3, -4, -5
 ENV_SCALARS, ENV_LOGGER_STATS = 16, 10
+STEP_STATS_DOUBLES = 1 + 4 * ENV_LOGGER_STATS     # MEL_ENV_STEP_STATS_DOUBLES: count, then per key mean, M2, min, max
 # scalars[b][k] / node_sets[b][k] / sel_sets[b][k] indices (melissa_hip.h MEL_S_* / MEL_SET_* / MEL_SEL_*)
 S_ORIGIN, S_SELECTION, S_SKIP, S_NUM_MOVES, S_WORLD_MSGS, S_NEW_ROUND, S_EPISODE, S_MOVE_CURSOR, \
     S_DECISIONS, S_DONE_COUNT, S_EPISODES_DONE, S_ERROR, S_EP_CURSOR = range(13)
@@ -41,7 +42,8 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
-           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss")
+           "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
+           "mel_env_step_stats")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -120,7 +122,7 @@ class MelEnvBatch(C.Structure):
                 ("log_capacity", C.c_int32), ("log_reserved", C.c_int32), ("log_cursor", C.c_void_p),
                 ("log_stats", C.c_void_p), ("log_meta", C.c_void_p),
                 ("plan_adj", C.c_void_p), ("plan_live", C.c_void_p), ("plan_u1", C.c_void_p), ("plan_u2", C.c_void_p),
-                ("plan_cnt", C.c_void_p), ("received_from", C.c_void_p)]
+                ("plan_cnt", C.c_void_p), ("step_stats", C.c_void_p), ("received_from", C.c_void_p)]
 
 
 class MelEpisodePool(C.Structure):
@@ -267,6 +269,8 @@ def load(build_if_missing: bool = True):
     lib.mel_replay_update_priority.argtypes = [C.POINTER(MelReplayPriority), i64, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.mel_env_observe.restype = i32
     lib.mel_env_observe.argtypes = [E, vp, i64, O, vp]
+    lib.mel_env_step_stats.restype = i32
+    lib.mel_env_step_stats.argtypes = [E, vp, i32, vp]
     lib.mel_mpr_sets.restype = i32
     lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz

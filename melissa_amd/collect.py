@@ -431,14 +431,79 @@ class DictOfSequenceSummaryStats:
         return cls(stats={k: SequenceSummaryStats.from_sequence(v) for k, v in stats.items() if len(v)})
 
 
+class StepStatsPool:
+    """Host model of the device's per-step ``logger_stats`` accumulator (``mel_env_batch.step_stats``, env.hip ``StepPool``):
+    per key the sample count, running mean, M2 (sum of squared deviations from the mean), min and max, merged by the Chan /
+    Welford rule in the kernels' own operation order -
+
+        n = na + nb;  d = mb - ma;  mean = ma + d * nb / n;  M2 = M2a + M2b + d * d * na * nb / n
+
+    - never sum and sum of squares (the std of ``total_messages_transmitted``-sized values over 1e5 rows must not cancel).
+    Count-gated: an empty side of a merge leaves the other untouched, the first sample sets mean = min = max = value and
+    M2 = 0, so a constant sequence has std == 0 exactly."""
+
+    def __init__(self, keys: int = _lib.ENV_LOGGER_STATS):
+        self.count = 0
+        self.mean, self.m2 = np.zeros(keys), np.zeros(keys)
+        self.min, self.max = np.zeros(keys), np.zeros(keys)
+
+    @classmethod
+    def from_row(cls, row) -> "StepStatsPool":
+        """One env's accumulator as the device stores it: ``[1 + 4 * keys]`` = count, then per key mean, M2, min, max."""
+        row = np.asarray(row, dtype=np.float64)
+        self = cls((len(row) - 1) // 4)
+        body = row[1:].reshape(-1, 4)
+        self.count = int(row[0])
+        self.mean, self.m2, self.min, self.max = (body[:, j].copy() for j in range(4))
+        return self
+
+    def to_row(self) -> np.ndarray:
+        return np.concatenate([[float(self.count)], np.stack([self.mean, self.m2, self.min, self.max], axis=1).reshape(-1)])
+
+    def add(self, values, count: int = 1) -> "StepStatsPool":
+        """``count`` identical samples (one value per key) in ONE merge: a block with n = count, mean = values, M2 = 0."""
+        block = StepStatsPool(len(self.mean))
+        v = np.asarray(values, dtype=np.float64)
+        block.count, block.mean, block.min, block.max = int(count), v.copy(), v.copy(), v.copy()
+        return self.merge(block)
+
+    def merge(self, other: "StepStatsPool") -> "StepStatsPool":
+        if other.count == 0:
+            return self
+        if self.count == 0:
+            self.count = other.count
+            self.mean, self.m2, self.min, self.max = other.mean.copy(), other.m2.copy(), other.min.copy(), other.max.copy()
+            return self
+        na, nb = float(self.count), float(other.count)
+        n = na + nb
+        d = other.mean - self.mean
+        self.mean = self.mean + d * nb / n
+        self.m2 = self.m2 + other.m2 + d * d * na * nb / n
+        self.min, self.max = np.minimum(self.min, other.min), np.maximum(self.max, other.max)
+        self.count += other.count
+        return self
+
+    def summary(self, keys=_lib.LOGGER_KEYS) -> dict:
+        """{key: SequenceSummaryStats} with the population std sqrt(M2 / n) of ``SequenceSummaryStats.from_sequence``; empty
+        without a sample."""
+        if self.count == 0:
+            return {}
+        std = np.sqrt(self.m2 / float(self.count))
+        return {key: SequenceSummaryStats(mean=float(self.mean[k]), std=float(std[k]), max=float(self.max[k]),
+                                          min=float(self.min[k])) for k, key in enumerate(keys)}
+
+
 @dataclasses.dataclass
 class CollectStatsWithInfo:
-    """The reference collectors' return value, field for field (collector.py:33-36 on top of [3P] tianshou ``CollectStats``;
-    built at multi_agent_collector.py:341-353).  ``returns[i]`` is episode i's reward sum as the env reports it at the
-    episode's last step (``logger_stats['episode_rewards_sum']``, graph.py:166-178); ``info.stats[key]`` summarises the
-    episodes' final ``logger_stats`` (the reference pools the ``logger_stats`` of EVERY collected step: same keys, a mean over
-    more samples).  ``episode_info``: the per-episode values behind ``info``.  The mapping protocol (``result["n/ep"]`` ...)
-    is the Tianshou-0.x spelling of the same numbers, kept for callers written against it."""
+    """The reference collectors' return value (collector.py:33-36 on top of [3P] tianshou ``CollectStats``; built at
+    multi_agent_collector.py:341-353) with the reference's field names.  ``returns[i]`` is episode i's reward sum as the env
+    reports it at the episode's last step (``logger_stats['episode_rewards_sum']``, graph.py:166-178), ``lens[i]`` its number
+    of rounds - not the reference's ``ep_rew`` / ``ep_len`` of the last saved sub-buffer.  ``info.stats[key]``: with a
+    collector built with ``stats="episodes"`` (the default) it summarises the episodes' FINAL ``logger_stats``; with
+    ``stats="steps"`` it is what the reference computes, the mean / std / max / min of ``logger_stats[key]`` over EVERY
+    collected env step (multi_agent_collector.py:276,316-322), pooled on the device, and ``n_info_rows`` is the number of
+    pooled steps.  ``episode_info``: the per-episode values (the rows behind ``info`` in "episodes" mode).  The mapping
+    protocol (``result["n/ep"]`` ...) is the Tianshou-0.x spelling of the same numbers, kept for callers written against it."""
     n_collected_episodes: int = 0
     n_collected_steps: int = 0
     collect_time: float = 0.0
@@ -449,6 +514,7 @@ class CollectStatsWithInfo:
     lens_stat: "SequenceSummaryStats | None" = None
     info: "DictOfSequenceSummaryStats | None" = None
     episode_info: dict = dataclasses.field(default_factory=dict)
+    n_info_rows: int = 0
 
     _ALIASES = {"n/ep": "n_collected_episodes", "n/st": "n_collected_steps"}
 
@@ -512,10 +578,17 @@ class Collector:
 
     def __init__(self, policy, venv: HipGraphVectorEnv, episodes_per_env: int = 16, seed: int = 0, eps: float = 0.0,
                  replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True,
-                 episode_stream: "bool | str | None" = None, ring: int = 16):
-        """``episode_stream`` / ``ring``: the episode supply, as :class:`RoundLoop` takes them."""
-        self.venv, self.policy, self.chunk = venv, policy, int(chunk)
+                 episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes"):
+        """``episode_stream`` / ``ring``: the episode supply, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
+        collect result summarises - ``"episodes"``: the final ``logger_stats`` row of each finished episode; ``"steps"``: the
+        ``logger_stats`` of every env step played during the call, as the reference pools them
+        (multi_agent_collector.py:276,316-322), accumulated by the env kernels (``HipGraphVectorEnv.enable_step_stats``)."""
+        if stats not in ("episodes", "steps"):
+            raise ValueError(f"stats={stats!r}: 'episodes' or 'steps'")
+        self.venv, self.policy, self.chunk, self.stats = venv, policy, int(chunk), stats
         venv.enable_episode_log(log_capacity)
+        if stats == "steps":
+            venv.enable_step_stats()            # before the loop: its `first` launch and every capture see the pool
         self.loop = RoundLoop(venv, policy, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=replay,
                               use_graph=use_graph, episode_stream=episode_stream, ring=ring)
         self._decisions = self.loop.counters()["decisions"]
@@ -526,6 +599,8 @@ class Collector:
         if (n_step is None) == (n_episode is None):
             raise ValueError("give exactly one of n_step / n_episode")        # the reference asserts the same
         self.venv.log_cursor.zero_()
+        if self.stats == "steps":
+            self.venv.step_stats.zero_()        # a device buffer: the captured round graphs keep replaying
         t0 = time.perf_counter()
         steps = episodes = 0
         with torch.no_grad():
@@ -542,7 +617,13 @@ class Collector:
         self.collect_step += steps
         self.collect_episode += total
         self.collect_time += dt
-        return result_from_episode_log(stats, meta, total, steps, dt)
+        result = result_from_episode_log(stats, meta, total, steps, dt)
+        if self.stats == "steps":
+            result.n_info_rows, pooled = self.venv.read_step_stats()
+            result.info = DictOfSequenceSummaryStats(stats=pooled)
+        else:
+            result.n_info_rows = len(stats)
+        return result
 
     def set_eps(self, eps: float) -> None:
         """Exploration rate of the following collects.  The rate is an argument of the selection fused into the forward's last
@@ -633,10 +714,13 @@ class MultiAgentCollector(Collector):
       greedy when False - [3P] ``DQNPolicy.exploration_noise`` through shared_policy.py:81-91, drawn on the device.
     * ``random=True``: uniformly random actions (eps = 1), as ``self._action_space[i].sample()`` does.
     * ``render``: not offered (the reference's matplotlib view, graph.py:466-484, is out of scope): a truthy value raises.
-    * ``no_grad``: accepted and ignored - the collect path never builds an autograd graph (the HIP forward has none)."""
+    * ``no_grad``: accepted and ignored - the collect path never builds an autograd graph (the HIP forward has none).
+    * ``stats="steps"``: ``info`` pools the ``logger_stats`` of every collected env step like the reference's (see
+      :class:`Collector`); the default ``"episodes"`` summarises the finished episodes' final rows."""
 
     def __init__(self, agents_num, policy=None, env=None, buffer=None, exploration_noise: bool = False, preprocess_fn=None,
-                 seed: int = 0, episodes_per_env: int = 16, chunk: int = 8, use_graph: bool = True, log_capacity: int = 65536):
+                 seed: int = 0, episodes_per_env: int = 16, chunk: int = 8, use_graph: bool = True, log_capacity: int = 65536,
+                 stats: str = "episodes"):
         if policy is None or env is None:
             raise TypeError("MultiAgentCollector needs policy= and env=")
         if preprocess_fn is not None:
@@ -649,7 +733,7 @@ class MultiAgentCollector(Collector):
         policy = getattr(policy, "policy", policy)          # a MultiAgentSharedPolicy manager wraps the one shared policy
         eps = float(getattr(policy, "eps", 0.0)) if exploration_noise else 0.0
         super().__init__(policy, env, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=buffer,
-                         log_capacity=log_capacity, chunk=chunk, use_graph=use_graph)
+                         log_capacity=log_capacity, chunk=chunk, use_graph=use_graph, stats=stats)
 
     @property
     def env_num(self) -> int:

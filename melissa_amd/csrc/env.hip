@@ -470,6 +470,64 @@ __device__ __forceinline__ void log_episode(const mel_env_batch& e, int b, const
     }
 }
 
+// ---- per-step logger_stats pool (mel_env_batch.step_stats) ---------------------------------------------------------------
+// What the reference's collectors pool: the logger_stats of every env.step (multi_agent_collector.py:276,316-322).  One env's
+// accumulator lives in its wavefront's registers for the launch: lane k < 10 holds key k (as write_info_stats lays the
+// values out), every lane the sample count.  Mean and M2 with the Chan / Welford merge, never sum and sum of squares.
+struct StepPool {
+    double n, mean, m2, mn, mx;
+};
+
+__device__ __forceinline__ void pool_load(const mel_env_batch& e, int b, int lane, StepPool& p) {
+    const double* src = e.step_stats + (size_t)b * MEL_ENV_STEP_STATS_DOUBLES;
+    const bool key = lane < MEL_ENV_LOGGER_STATS;
+    p.n = src[0];
+    p.mean = key ? src[1 + 4 * lane] : 0.0, p.m2 = key ? src[2 + 4 * lane] : 0.0;
+    p.mn = key ? src[3 + 4 * lane] : 0.0, p.mx = key ? src[4 + 4 * lane] : 0.0;
+}
+
+__device__ __forceinline__ void pool_store(const mel_env_batch& e, int b, int lane, const StepPool& p) {
+    double* dst = e.step_stats + (size_t)b * MEL_ENV_STEP_STATS_DOUBLES;
+    if (lane == 0) dst[0] = p.n;
+    if (lane < MEL_ENV_LOGGER_STATS) {
+        dst[1 + 4 * lane] = p.mean, dst[2 + 4 * lane] = p.m2;
+        dst[3 + 4 * lane] = p.mn, dst[4 + 4 * lane] = p.mx;
+    }
+}
+
+// merge of two accumulators (b into a); an empty side leaves the other as it is (the count gates mean / M2 / min / max)
+__device__ __forceinline__ void pool_merge(StepPool& a, const StepPool& b) {
+    if (b.n == 0.0) return;
+    if (a.n == 0.0) {
+        a = b;
+        return;
+    }
+    const double n = a.n + b.n;
+    const double d = b.mean - a.mean;
+    a.mean = a.mean + d * b.n / n;
+    a.m2 = a.m2 + b.m2 + d * d * a.n * b.n / n;
+    a.mn = b.mn < a.mn ? b.mn : a.mn;
+    a.mx = b.mx > a.mx ? b.mx : a.mx;
+    a.n = n;
+}
+
+// `count` identical samples of value v (this lane's key) in one merge: a block with n = count, mean = v, M2 = 0
+__device__ __forceinline__ void pool_add(StepPool& p, double v, int count) {
+    pool_merge(p, StepPool{(double)count, v, 0.0, v, v});
+}
+
+// One sample = the ten values STORED in infos[agent] (PettingZooEnv.step -> env.last(): the slot as it is, stale or not),
+// nothing when the slot holds no logger_stats (d.pop('logger_stats', {})) or there is no selection.  `valid`: the
+// MEL_SEL_INFO_VALID set as it is at that sub-step.
+template <int W>
+__device__ __forceinline__ void pool_sample(const mel_env_batch& e, int b, int agent, const NodeSet<W>& valid, int lane,
+                                            StepPool& p) {
+    if (agent < 0 || !ns_test(valid, agent)) return;
+    const double v = lane < MEL_ENV_LOGGER_STATS
+                         ? e.info_stats[((size_t)b * e.n_nodes + agent) * MEL_ENV_LOGGER_STATS + lane] : 0.0;
+    pool_add(p, v, 1);
+}
+
 // GraphEnv.step graph.py:303-359 (+ the sticky reward copy of [3P] PettingZooEnv.step)
 // returns true when this step completed the round and ran the world step
 template <int W>
@@ -699,7 +757,8 @@ __device__ unsigned long long g_env_prof[9];
 #define ENV_MARK(x) asm volatile("s_nop 0" ::"s"(x))
 #endif
 
-template <int W>
+// POOL: the per-step logger_stats pool is on (mel_env_batch.step_stats != NULL); without it the kernel is the code it was
+template <int W, bool POOL>
 __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= a.env.n_envs) return;
@@ -712,6 +771,8 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
     const unsigned long long p0 = ENV_T();
 #endif
     env_load(a.env, b, lane, s);
+    StepPool sp{};
+    if (POOL) pool_load(a.env, b, lane, sp);
 #ifdef MEL_ENV_PROF
     ENV_MARK(s.sel);
     asm volatile("s_nop 0" ::"v"(s.px[0]), "v"(s.steps[0]));
@@ -756,6 +817,16 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
             const NodeSet<W> dead = s.agents & s.terminated;
             if (ns_any(dead) && s.skip >= 0 && s.sel == ns_lowest(dead) && ns_any(s.agents & ~dead) &&
                 s.done_count + ns_count(dead) - 1 < n && s.error == 0) {
+                if (POOL) {
+                    // one sample per dead step: the slot of the agent that becomes the selection - the next dead agent, at
+                    // last skip - with the validity of that sub-step (a dead step deletes only its own agent's slot)
+                    NodeSet<W> rest = dead, valid = s.info_valid;
+                    while (ns_any(rest)) {
+                        valid &= ~ns_bit<W>(ns_lowest(rest));
+                        ns_clear_lowest(rest);
+                        pool_sample<W>(a.env, b, ns_any(rest) ? ns_lowest(rest) : s.skip, valid, lane, sp);
+                    }
+                }
                 const NodeSet<W> keep = ~dead;
                 s.sel_active &= keep, s.alive &= keep, s.terminated &= keep, s.info_valid &= keep, s.agents &= keep;
                 s.done_count += ns_count(dead) - 1;
@@ -792,6 +863,8 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
                     write_info_stats(a.env, b, nxt, s, lane);
                 }
                 s.info_valid |= later;
+                // k - 1 identical samples: each early step makes the next agent the selection with the info just written
+                if (POOL) pool_add(sp, lane < MEL_ENV_LOGGER_STATS ? s.info_val : 0.0, ns_count(early));
                 MEL_W_FOR(h) if (ns_mine(s.alive, lane, h)) s.pz_reward[h] = s.reward[h];
                 s.new_round = 0;                                     // the first observe of the round (:209-211)
                 s.sel = last;
@@ -821,6 +894,7 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
             const unsigned long long q1 = ENV_T();
 #endif
             const int r = env_observe(a.env, b, s, none, 0, lane);
+            if (POOL) pool_sample<W>(a.env, b, s.sel, s.info_valid, lane, sp);
 #ifdef MEL_ENV_PROF
             ENV_MARK(r);
             const unsigned long long q2 = ENV_T();
@@ -873,6 +947,7 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
     // agents that will act in the coming round: exactly the selector's active set (selector.py:22-34,43-44)
     if (lane == 0) ns_store<W>(a.live, b, s.sel_active);
     env_store(a.env, b, lane, s);
+    if (POOL) pool_store(a.env, b, lane, sp);
     // optional plan sink: what the next forward's plan_masks launch would compute from the obs this launch wrote (the
     // obs positions are (float)px, (float)py: write_obs_matrix) and the active set it just published
     if (a.env.plan_adj) {
@@ -923,6 +998,12 @@ __global__ __launch_bounds__(256) void env_kernel(StepArgs a) {
         env_step(a.env, a.pool, b, s, a.actions[row], lane);
         if (a.has_out) {
             const int r = env_observe(a.env, b, s, a.out, row, lane);
+            if (a.env.step_stats) {                // per-step logger_stats pool: one sample per call
+                StepPool sp;
+                pool_load(a.env, b, lane, sp);
+                pool_sample<W>(a.env, b, s.sel, s.info_valid, lane, sp);
+                pool_store(a.env, b, lane, sp);
+            }
             if (a.episode_table) {
                 if (r & 1) s.done_count += 1;
                 // multi_agent_collector.py:261-264: episode over -> reset this env
@@ -956,6 +1037,40 @@ __global__ __launch_bounds__(256) void mpr_sets_kernel(const uint64_t* one_hop, 
     }
     mpr_of<W>(hop, on, lane, m);
     MEL_W_FOR(h) if (on[h]) ns_store<W>(out, (size_t)g * n + lane + 64 * h, m[h]);
+}
+
+// mel_env_step_stats: one workgroup merges the B per-env accumulators in a fixed order - thread t folds envs t, t + 256, ...
+// in index order, then a fixed pairwise tree in LDS - one key at a time; thread 0 writes count | mean, std, max, min.
+// reset: every thread empties the accumulators it read (nobody else reads them).
+__global__ __launch_bounds__(256) void step_stats_kernel(double* acc, int n_envs, double* out, int reset) {
+    __shared__ StepPool part[256];
+    const int t = threadIdx.x;
+    for (int k = 0; k < MEL_ENV_LOGGER_STATS; ++k) {
+        StepPool p{};
+        for (int b = t; b < n_envs; b += 256) {
+            const double* src = acc + (size_t)b * MEL_ENV_STEP_STATS_DOUBLES;
+            pool_merge(p, StepPool{src[0], src[1 + 4 * k], src[2 + 4 * k], src[3 + 4 * k], src[4 + 4 * k]});
+        }
+        part[t] = p;
+        __syncthreads();
+        for (int half = 128; half > 0; half >>= 1) {
+            if (t < half) pool_merge(part[t], part[t + half]);
+            __syncthreads();
+        }
+        if (t == 0) {
+            const StepPool r = part[0];
+            const bool any = r.n > 0.0;
+            if (k == 0) out[0] = r.n;
+            out[1 + 4 * k] = any ? r.mean : 0.0;
+            out[2 + 4 * k] = any ? sqrt(r.m2 / r.n) : 0.0;
+            out[3 + 4 * k] = any ? r.mx : 0.0;
+            out[4 + 4 * k] = any ? r.mn : 0.0;
+        }
+        __syncthreads();
+    }
+    if (reset)
+        for (int b = t; b < n_envs; b += 256)
+            for (int c = 0; c < MEL_ENV_STEP_STATS_DOUBLES; ++c) acc[(size_t)b * MEL_ENV_STEP_STATS_DOUBLES + c] = 0.0;
 }
 
 static mel_status check_env(const mel_env_batch* env, int64_t n) {
@@ -1038,6 +1153,7 @@ mel_status mel_env_bind(mel_env_batch* env, int32_t n_envs, int32_t n_nodes, voi
     env->log_meta = keep.log_meta;
     env->plan_adj = keep.plan_adj, env->plan_live = keep.plan_live, env->plan_u1 = keep.plan_u1, env->plan_u2 = keep.plan_u2,
     env->plan_cnt = keep.plan_cnt;
+    env->step_stats = keep.step_stats;
     return MEL_OK;
 }
 
@@ -1108,9 +1224,25 @@ mel_status mel_env_round(mel_env_batch* env, const mel_episode_pool* pool, const
         a.replay = *replay;
     }
     StageScope t(MEL_STAGE_ENV_STEP, static_cast<hipStream_t>(stream));
-    if (env->n_nodes > 64) MEL_LAUNCH(env_round_kernel<2>, dim3((env->n_envs + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    else MEL_LAUNCH(env_round_kernel<1>, dim3((env->n_envs + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    const dim3 grid((env->n_envs + 3) / 4);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (env->step_stats) {
+        if (env->n_nodes > 64) MEL_LAUNCH((env_round_kernel<2, true>), grid, dim3(256), 0, s, a);
+        else MEL_LAUNCH((env_round_kernel<1, true>), grid, dim3(256), 0, s, a);
+    } else {
+        if (env->n_nodes > 64) MEL_LAUNCH((env_round_kernel<2, false>), grid, dim3(256), 0, s, a);
+        else MEL_LAUNCH((env_round_kernel<1, false>), grid, dim3(256), 0, s, a);
+    }
     return check_launch("env_round");
+}
+
+mel_status mel_env_step_stats(const mel_env_batch* env, double* out, int32_t reset, void* stream) {
+    if (!env || !out) return fail(MEL_ERR_INVALID_ARG, "mel_env_step_stats: null argument");
+    if (mel_status st = check_env(env, env->n_envs)) return st;
+    if (!env->step_stats) return fail(MEL_ERR_INVALID_ARG, "mel_env_step_stats: the per-step pool is off (step_stats is null)");
+    clear_stale_error();
+    MEL_LAUNCH(step_stats_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), env->step_stats, env->n_envs, out, reset);
+    return check_launch("env_step_stats");
 }
 
 // ---- replay sampling: one launch instead of ~150 small index launches (replay.RoundReplay.sample) ---------------------------------

@@ -264,6 +264,46 @@ class HipGraphVectorEnv:
             self.log_cursor.zero_()
         return out
 
+    def enable_step_stats(self):
+        """The per-step ``logger_stats`` pool (``mel_env_batch.step_stats``): from now on every AEC sub-step the env kernels
+        play (``mel_env_round``, and ``mel_env_step`` with an output) adds the ``logger_stats`` of its observation to its
+        env's accumulator - what the reference's collectors pool (multi_agent_collector.py:276,316-322).  Starts empty; a
+        graph captured BEFORE this call keeps replaying the kernel without the pool."""
+        self.step_stats = torch.zeros(self.env_num, _lib.STEP_STATS_DOUBLES, dtype=torch.float64, device=self.device)
+        self._step_stats_out = torch.zeros(_lib.STEP_STATS_DOUBLES, dtype=torch.float64, device=self.device)
+        self.env.step_stats = self.step_stats.data_ptr()
+
+    def read_step_stats(self, reset: bool = False, per_env: bool = False, on_host: bool = False):
+        """-> (sample count, {key: SequenceSummaryStats}) over every step pooled since the pool was last emptied, merged over
+        the envs on the device in a fixed order (``mel_env_step_stats``; keys without a sample are absent, so an empty pool
+        gives ``(0, {})``).  ``per_env=True``: the raw accumulators instead, float64 ``[B, 41]`` on the host - per env the
+        count, then per key mean, M2, min, max (``collect.StepStatsPool.from_row`` reads a row).  ``on_host=True``: merge
+        those rows with the host model of the accumulator instead of the device launch (an explicit choice, never a
+        fallback).  ``reset`` empties the pool: in the launch that reads it on the default path; with ``per_env`` / ``on_host``
+        the rows are copied first and zeroed by a fill of their own afterwards.  Synchronises."""
+        from ..collect import SequenceSummaryStats, StepStatsPool
+        if getattr(self, "step_stats", None) is None:
+            raise RuntimeError("read_step_stats(): the per-step pool is off (enable_step_stats())")
+        if per_env or on_host:
+            rows = self.step_stats.cpu().numpy()
+            if reset:
+                self.step_stats.zero_()
+            if per_env:
+                return rows
+            pool = StepStatsPool()
+            for row in rows:
+                pool.merge(StepStatsPool.from_row(row))
+            return pool.count, pool.summary()
+        _lib.check(self.lib.mel_env_step_stats(C.byref(self.env), self._step_stats_out.data_ptr(), int(bool(reset)),
+                                               self._stream()), "mel_env_step_stats")
+        out = self._step_stats_out.cpu().numpy()
+        count = int(out[0])
+        if count == 0:
+            return 0, {}
+        return count, {key: SequenceSummaryStats(mean=float(out[1 + 4 * k]), std=float(out[2 + 4 * k]),
+                                                 max=float(out[3 + 4 * k]), min=float(out[4 + 4 * k]))
+                       for k, key in enumerate(LOGGER_KEYS)}
+
     def make_sampler(self, seed, env: int = 0) -> EpisodeSampler:
         """An episode sampler with this env's settings (graph pool size, evaluation schedule, scripted ratio, ...)
         and its own generator seeded ``seed`` - what the device-resident loops pre-draw their episode pools with.

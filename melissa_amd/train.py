@@ -189,7 +189,7 @@ def replay_rounds_for(buffer_size: int, envs: int, n_nodes: int) -> int:
 
 
 def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, step_per_epoch, rank, world, device, best_path,
-                last_path, pace=None):
+                last_path, pace=None, pooled=None):
     """The reference's training structure ([3P] tianshou ``OffpolicyTrainer`` as l_dgn.py:246-261 configures it): evaluate, then
     ``epoch`` times [update iterations until ``step_per_epoch`` more env steps are collected; evaluate; keep the best policy], then
     save the last one.  env steps = decisions x ``world``, the decisions being this rank's - with several ranks the smallest
@@ -205,7 +205,9 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     evaluation's env step; 0 or many), and at the end of an epoch the count read with a synchronise settles the rest before
     the evaluation - ``updates_done == floor(update_per_step * (env_step - base))`` at every epoch boundary.  Every rank
     derives the number from the same agreed count, so all take the same updates.  The target-network sync keeps counting
-    updates.  Epoch records then also carry ``update_debt`` (0)."""
+    updates.  Epoch records then also carry ``update_debt`` (0).
+    ``pooled()`` (``--collect-stats steps``): the means of the ``logger_stats`` of every env step this rank's training envs played
+    since the last call; every epoch record carries them (``train_info_rows``, ``train_<key>``)."""
     import torch
     from . import parallel
     if rank == 0:
@@ -215,6 +217,8 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     def test(index, env_step, **more):
         nonlocal best
         rec = dict(epoch=index, env_step=env_step, eps=loop.eps_now()[1], **more)
+        if pooled is not None:
+            rec.update(pooled())
         stats = evaluate()
         if rank == 0:
             is_best = best is None or stats["rew"] > best[1]   # (the first evaluation sets the best: [3P] BaseTrainer.reset)
@@ -283,7 +287,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
           heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
-          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1):
+          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes"):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -312,7 +316,15 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     ``replay_rounds``).
     ``test_envs`` (epoch mode): 1 evaluates with one env, a host-drawn episode table and eager rounds; more evaluates with
     ``min(test_envs, test_num)`` envs that share one pass over the list of test seeds, drawn on the device and replayed from a
-    HIP graph (:func:`_evaluate_spread`).  The epoch records carry the number used as ``test_envs``."""
+    HIP graph (:func:`_evaluate_spread`).  The epoch records carry the number used as ``test_envs``.
+    ``collect_stats``: "steps" pools the ``logger_stats`` of every env step the training envs play on the device, as the
+    reference's training collects do (multi_agent_collector.py:276,316-322; ``HipGraphVectorEnv.enable_step_stats``), and
+    reports their means (``train_info_rows``, ``train_<key>``: per epoch record, or over the whole run in the fixed-updates
+    mode; each rank pools its own envs, rank 0 reports).  An epoch record is written before that epoch's evaluation and its
+    pool is read and emptied there, so it holds the training rounds since the previous record and never an evaluation's (those
+    run on envs of their own); the record of epoch 0 holds the pre-fill rounds.  "episodes" (the default) pools nothing."""
+    if collect_stats not in ("episodes", "steps"):
+        raise ValueError(f"collect_stats={collect_stats!r}: 'episodes' or 'steps'")
     if int(test_envs) < 1:
         raise ValueError(f"test_envs={test_envs} must be >= 1")
     if update_per_step is not None:
@@ -350,6 +362,13 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False, heuristic=heuristic,
                              scripted_agents_ratio=scripted_agents_ratio)
+    pooled = None
+    if collect_stats == "steps":
+        venv.enable_step_stats()                               # before the loop is built: every captured round pools
+
+        def pooled():
+            count, stats = venv.read_step_stats(reset=True)
+            return dict(train_info_rows=count, **{f"train_{k}": v.mean for k, v in stats.items()})
     paced = update_per_step is not None
     if buffer_size is not None:
         replay_rounds = replay_rounds_for(buffer_size, envs, n_nodes)
@@ -430,7 +449,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         losses, dt, updates, extra = _run_epochs(loop, policy, iteration, evaluate, capture, int(epoch), int(step_per_epoch), rank,
                                                  world, device, os.path.join(weights_dir, f"{name}_best.pth"),
                                                  os.path.join(weights_dir, f"{name}_last.pth"),
-                                                 pace=(collect, update, float(update_per_step)) if paced else None)
+                                                 pace=(collect, update, float(update_per_step)) if paced else None,
+                                                 pooled=pooled)
         extra["param_checksum_start"] = checksum_start
         if paced:
             extra.update(update_per_step=float(update_per_step), rounds_per_collect=rounds_per_update,
@@ -448,6 +468,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                warmup_updates=warmup_updates, heuristic=heuristic, scripted_agents_ratio=float(scripted_agents_ratio),
                episode_supply=loop.supply.describe())
     out.update(extra)
+    if pooled is not None and epoch is None:
+        out.update(pooled())
     # replicas must be identical after averaged-gradient steps
     same = parallel.all_reduce_max(checksum, device) == parallel.all_reduce_max(-checksum, device) * -1
     out["replicas_identical"] = bool(same)
@@ -501,6 +523,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--test-envs", type=int, default=1,
                     help="envs of an evaluation: 1 plays the --test-num episodes one after another; more share them out, draw "
                          "them on the device and replay the rounds from a HIP graph")
+    ap.add_argument("--collect-stats", choices=["episodes", "steps"], default="episodes",
+                    help="steps: pool the logger_stats of every env step of the training envs on the device (the reference's "
+                         "statistic) and report their means")
     ap.add_argument("--logdir", type=str, default="log")
     ap.add_argument("--model-name", type=str, default=default_model_name())
     ap.add_argument("--resume-path", type=str, default=None)
@@ -523,7 +548,7 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
                 seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq,
                 update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size,
-                test_envs=a.test_envs)
+                test_envs=a.test_envs, collect_stats=a.collect_stats)
 
 
 def parse_args(argv=None) -> argparse.Namespace:

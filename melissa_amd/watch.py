@@ -30,7 +30,12 @@ from .train import N_DGN_NETWORK, build_network
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
-          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False):
+          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes"):
+    """``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
+    statistic, pooled on the device; ``n_info_rows`` steps) instead of over the episodes' final rows.  Not with ``spread``:
+    the envs that finish their share early keep playing, and those surplus episodes would enter the pool."""
+    if spread and collect_stats != "episodes":
+        raise ValueError("collect_stats='steps' is not offered with spread: surplus episodes would enter the pool")
     torch.manual_seed(seed)
     net = build_network(model, n_nodes, device)
     policy = DQNPolicy(net, target_update_freq=1)
@@ -48,11 +53,12 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed)
     else:
         per_env = -(-episodes // envs) + 2
-        col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64)
+        col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64,
+                        stats=collect_stats)
         out = col.collect(n_episode=episodes)
     # the scalars of the collect result (counts, speed, mean return / length, mean of every logger_stats key) as a plain dict
     keys = ["n/ep", "n/st", "collect_time", "collect_speed"] + (["rew", "len"] if out.returns_stat is not None else []) \
-        + list(out.info.stats)
+        + list(out.info.stats) + (["n_info_rows"] if collect_stats == "steps" else [])
     return {k: out[k] for k in keys}
 
 
@@ -72,13 +78,19 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--spread", action="store_true", default=False,
                     help="share the --episodes test seeds out over the --envs envs (each played once) instead of every env "
                          "walking the list from the top")
+    ap.add_argument("--collect-stats", choices=["episodes", "steps"], default="episodes",
+                    help="steps: the logger_stats means are taken over every env step played (the reference's statistic), not "
+                         "over the episodes' final rows; not with --spread")
     return ap
 
 
 def main(argv=None):
-    a = arg_parser().parse_args(argv)
+    ap = arg_parser()
+    a = ap.parse_args(argv)
+    if a.spread and a.collect_stats != "episodes":
+        ap.error("--collect-stats steps is not offered with --spread (surplus episodes would enter the pool)")
     print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype, heuristic=a.heuristic,
-                           scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread)))
+                           scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread, collect_stats=a.collect_stats)))
 
 
 if __name__ == "__main__":
