@@ -16,6 +16,7 @@
 // Scripted agents run the deterministic heuristics of heuristics/core.py and mpr.py (MEL_HEURISTIC_*).
 #include "common.hpp"
 #include "plan_masks.hpp"
+#include "kprof.hpp"
 
 namespace mel {
 
@@ -272,20 +273,22 @@ __device__ __forceinline__ void selector_enable(Env<W>& s, const NodeSet<W>& age
     s.sel_active = (s.sel_active & ~agents) | (agents & can);
 }
 
-#ifdef MEL_ENV_PROF
+#ifdef MEL_ENV_PROF           // tuning builds: cycle counters in world_step and env_round_kernel (kprof.hpp, tools/env_prof.py)
+constexpr bool ENV_PROF = true;
+#else
+constexpr bool ENV_PROF = false;
+#endif
 // finer split of the world step (wave 0 lane 0 of every eighth env adds): [0] relay + scripted, [1] move + all-pairs edges,
 // [2] two-hop masks, [3] calls
 __device__ unsigned long long g_world_prof[4];
-#endif
 
 // World.step core.py:225-266
 template <int W>
 __device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_episode_pool& pool, int b, Env<W>& s,
                                            int lane) {
     const int n = e.n_nodes;
-#ifdef MEL_ENV_PROF
-    const unsigned long long wp0 = __builtin_readcyclecounter();
-#endif
+    KLaps<ENV_PROF, 4> prof;
+    prof.mark();
     s.info_valid_cache = 0;                                  // message counters, coverage and (dynamic graph) degrees change here
     // :226-234 scripted agents: action = heuristic(agent) (only mpr returns a relay mask: the relays_for pass :236-243
     // runs with it alone)
@@ -327,11 +330,7 @@ __device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_epi
     }
     if (e.heuristic == MEL_HEURISTIC_MPR)
         MEL_W_FOR(h) if (lane + 64 * h < n) MEL_W_FOR(k) e.received_from[((size_t)b * n + lane + 64 * h) * W + k] = node_rows<W>()[lane + 64 * h][k];
-#ifdef MEL_ENV_PROF
-    asm volatile("s_nop 0" ::"s"(s.has_msg.w[0]), "v"(s.received[0]));
-    const unsigned long long wp1 = __builtin_readcyclecounter();
-    unsigned long long wp2 = wp1, wp3 = wp1;
-#endif
+    prof.lap(0, ksgpr(s.has_msg.w[0]), s.received[0]);
     // :256-257 move_graph -> update_position + one/two hop recompute (core.py:281-341)
     if (e.dynamic_graph) {
         int mv = s.move_cursor;
@@ -348,22 +347,12 @@ __device__ __forceinline__ void world_step(const mel_env_batch& e, const mel_epi
         }
         s.move_cursor += 1;
         geometric_one_hop<W>(s.px, s.py, lane, n, s.one_hop);
-#ifdef MEL_ENV_PROF
-        asm volatile("s_nop 0" ::"v"(s.one_hop[0].w[0]));
-        wp2 = __builtin_readcyclecounter();
-#endif
+        prof.lap(1, s.one_hop[0].w[0]);
         two_hop_of<W>(s.one_hop, lane, n, s.two_hop);
-#ifdef MEL_ENV_PROF
-        asm volatile("s_nop 0" ::"v"(s.two_hop[0].w[0]));
-        wp3 = __builtin_readcyclecounter();
-#endif
+        prof.lap(2, s.two_hop[0].w[0]);
     }
-#ifdef MEL_ENV_PROF
-    if (lane == 0 && (blockIdx.x & 1) == 0 && (threadIdx.x >> 6) == 0) {
-        atomicAdd(&g_world_prof[0], wp1 - wp0), atomicAdd(&g_world_prof[1], wp2 - wp1), atomicAdd(&g_world_prof[2], wp3 - wp2);
-        atomicAdd(&g_world_prof[3], 1ull);
-    }
-#endif
+    prof.add(3, 1);
+    prof.flush(g_world_prof, lane == 0 && (blockIdx.x & 1) == 0 && (threadIdx.x >> 6) == 0);
     // :260-261 -> Agent.update_two_hop_cover_from_one_hopper (core.py:94-102)
     MEL_W_FOR(h) {
         s.cover[h] = ns_count(s.two_hop[h] & (s.has_msg | s.origin_set));
@@ -748,14 +737,10 @@ __device__ __forceinline__ void env_reset_from_snapshot(const mel_env_batch& e, 
     write_obs_matrix(e, b, s, lane);
 }
 
-#ifdef MEL_ENV_PROF
 // tuning builds: cycles a sample of the env wavefronts spends in [0] state load, [1] the round loop, [2] the env_step call
 // that runs the world step, [3] the other env_step calls, [4] env_observe, [5] episode end (log + reset), [6] state store;
 // [7] wavefronts sampled, [8] loop iterations                                               (tools/env_prof.py)
 __device__ unsigned long long g_env_prof[9];
-#define ENV_T() __builtin_readcyclecounter()
-#define ENV_MARK(x) asm volatile("s_nop 0" ::"s"(x))
-#endif
 
 // POOL: the per-step logger_stats pool is on (mel_env_batch.step_stats != NULL); without it the kernel is the code it was
 template <int W, bool POOL>
@@ -766,18 +751,12 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
     const int n = a.env.n_nodes;
     if (a.round_counter && b == 0 && lane == 0 && !a.first) atomicAdd(a.round_counter, 1u);
     Env<W> s;
-#ifdef MEL_ENV_PROF
-    unsigned long long pw = 0, ps = 0, po = 0, pr = 0, pit = 0;
-    const unsigned long long p0 = ENV_T();
-#endif
+    KLaps<ENV_PROF, 9> prof;
+    prof.mark();
     env_load(a.env, b, lane, s);
     StepPool sp{};
     if (POOL) pool_load(a.env, b, lane, sp);
-#ifdef MEL_ENV_PROF
-    ENV_MARK(s.sel);
-    asm volatile("s_nop 0" ::"v"(s.px[0]), "v"(s.steps[0]));
-    const unsigned long long p1 = ENV_T();
-#endif
+    const auto loop_start = prof.lap(0, ksgpr(s.sel), s.px[0], s.steps[0]);
     const mel_env_obs none{};
     if (!a.first) {
         const NodeSet<W> live_in = ns_uniform(ns_load<W>(a.live, b));
@@ -884,22 +863,13 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
                 }
                 action = node_i32<W>(my_action, sel);
             }
-#ifdef MEL_ENV_PROF
-            const unsigned long long q0 = ENV_T();
-#endif
+            prof.mark();
             const bool world = env_step(a.env, a.pool, b, s, action, lane, rec_next);
-#ifdef MEL_ENV_PROF
-            ENV_MARK(s.sel);
-            asm volatile("s_nop 0" ::"v"(s.reward[0]), "v"(s.one_hop[0].w[0]));
-            const unsigned long long q1 = ENV_T();
-#endif
+            prof.lap(world ? 2 : 3, ksgpr(s.sel), s.reward[0], s.one_hop[0].w[0]);
             const int r = env_observe(a.env, b, s, none, 0, lane);
             if (POOL) pool_sample<W>(a.env, b, s.sel, s.info_valid, lane, sp);
-#ifdef MEL_ENV_PROF
-            ENV_MARK(r);
-            const unsigned long long q2 = ENV_T();
-            (world ? pw : ps) += q1 - q0, po += q2 - q1, pit += 1;
-#endif
+            prof.lap(4, ksgpr(r));
+            prof.add(8, 1);
             if (world && rec_next) {          // the world step just ran: rewards / terminations of this round
                 MEL_W_FOR(h) if (lane + 64 * h < n)
                     a.replay.rew[rec * n + lane + 64 * h] = ns_mine(live_in, lane, h) ? (float)s.reward[h] : 0.f;
@@ -922,28 +892,20 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
             if (r & 1) s.done_count += 1;
             if ((r & 1) && ((r & 2) || s.done_count == n)) {                  // episode over
                 s.episodes_done += 1;
-#ifdef MEL_ENV_PROF
-                const unsigned long long r0 = ENV_T();
-#endif
+                prof.mark();
                 log_episode(a.env, b, s, lane);
                 if (a.pool.produced && s.ep_cursor >= uniform_i32(a.pool.produced[b])) s.error |= MEL_ENV_ERR_EPISODE_UNDERRUN;
                 const int ep = uniform_i32(a.episode_table[(size_t)b * a.table_stride + (s.ep_cursor % a.table_stride)]);
                 if (a.has_snap) env_reset_from_snapshot(a.env, a.snap, b, s, ep, lane);
                 else env_reset(a.env, a.pool, b, s, ep, 0, lane);
                 env_observe(a.env, b, s, none, 0, lane);
-#ifdef MEL_ENV_PROF
-                ENV_MARK(s.sel);
-                asm volatile("s_nop 0" ::"v"(s.px[0]), "v"(s.one_hop[0].w[0]));
-                pr += ENV_T() - r0;
-#endif
+                prof.lap(5, ksgpr(s.sel), s.px[0], s.one_hop[0].w[0]);
                 break;
             }
             if (r & 4) break;                                                  // world step done: new round
         }
     }
-#ifdef MEL_ENV_PROF
-    const unsigned long long p2 = ENV_T();
-#endif
+    prof.since(1, loop_start);
     // agents that will act in the coming round: exactly the selector's active set (selector.py:22-34,43-44)
     if (lane == 0) ns_store<W>(a.live, b, s.sel_active);
     env_store(a.env, b, lane, s);
@@ -956,15 +918,10 @@ __global__ __launch_bounds__(256) void env_round_kernel(RoundArgs a) {
         plan_masks_env<W>(x, y, s.sel_active & ns_full<W>(n), a.env.plan_u1 ? 1 : -1, b, a.env.n_envs, n, lane,
                           PlanSink{a.env.plan_adj, a.env.plan_live, a.env.plan_u1, a.env.plan_u2, a.env.plan_cnt});
     }
-#ifdef MEL_ENV_PROF
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long p3 = ENV_T();
-    if (lane == 0 && (b & 7) == 0 && !a.first) {
-        atomicAdd(&g_env_prof[0], p1 - p0), atomicAdd(&g_env_prof[1], p2 - p1), atomicAdd(&g_env_prof[2], pw);
-        atomicAdd(&g_env_prof[3], ps), atomicAdd(&g_env_prof[4], po), atomicAdd(&g_env_prof[5], pr);
-        atomicAdd(&g_env_prof[6], p3 - p2), atomicAdd(&g_env_prof[7], 1ull), atomicAdd(&g_env_prof[8], pit);
-    }
-#endif
+    prof.wait_vmem();
+    prof.lap(6);
+    prof.add(7, 1);
+    prof.flush(g_env_prof, lane == 0 && (b & 7) == 0 && !a.first);
 }
 
 struct StepArgs {
@@ -1123,6 +1080,11 @@ static EnvLayout carve_env(int32_t B, int32_t n, void* state) {
     L.e.received_from = c.take<uint64_t>(BN * SW);     // last: the offsets above do not depend on it
     L.bytes = c.off;
     return L;
+}
+
+// this translation unit's share of mel_debug_prof_read (fwd.hip)
+int32_t kprof_read_env(int32_t family, unsigned long long* out, int32_t cap) {
+    return family == KPROF_WORLD ? kprof_read(ENV_PROF, g_world_prof, out, cap) : kprof_read(ENV_PROF, g_env_prof, out, cap);
 }
 
 }  // namespace mel
@@ -1489,26 +1451,6 @@ mel_status mel_wait_counter(const uint32_t* counter, uint32_t target, uint32_t t
     clear_stale_error();
     MEL_LAUNCH(wait_counter_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), counter, target, timeout_us);
     return check_launch("wait_counter");
-}
-
-// tuning builds only (-DMEL_ENV_PROF): read and reset the round kernel's cycle counters (tools/env_prof.py)
-void mel_debug_world_prof(unsigned long long* out4) {
-#ifdef MEL_ENV_PROF
-    (void)hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_world_prof), 4 * sizeof(unsigned long long));
-    unsigned long long z[4] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_world_prof), z, sizeof(z));
-#else
-    for (int i = 0; i < 4; ++i) out4[i] = 0;
-#endif
-}
-void mel_debug_env_prof(unsigned long long* out9) {
-#ifdef MEL_ENV_PROF
-    (void)hipMemcpyFromSymbol(out9, HIP_SYMBOL(g_env_prof), 9 * sizeof(unsigned long long));
-    unsigned long long z[9] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_env_prof), z, sizeof(z));
-#else
-    for (int i = 0; i < 9; ++i) out9[i] = 0;
-#endif
 }
 
 mel_status mel_mpr_sets(const uint64_t* one_hop, int32_t n_graphs, int32_t n_nodes, uint64_t* mpr_out, void* stream) {

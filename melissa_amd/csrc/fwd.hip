@@ -714,61 +714,21 @@ using namespace mel;
 extern "C" {
 
 const char* mel_last_error(void) { return g_err; }
-// tuning builds only (-DMEL_FIN_PROF): read and reset the head finish kernel's cycle counters
-void mel_debug_fin_prof(unsigned long long* out5) {
-#ifdef MEL_FIN_PROF
-    (void)hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_fin_prof), 5 * sizeof(unsigned long long));
-    unsigned long long z[5] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fin_prof), z, sizeof(z));
-#else
-    for (int i = 0; i < 5; ++i) out5[i] = 0;
-#endif
+// Tuning aid (kprof.hpp, tools/kprof.py): read and zero the in-kernel cycle counters of one KprofFamily.  Returns the family's
+// slot count (at most `cap` slots are copied), 0 if this build does not instrument it (-DMEL_*_PROF), -1 if there is no such family.
+int32_t mel_debug_prof_read(int32_t family, unsigned long long* out, int32_t cap) {
+    switch (family) {
+        case KPROF_WORLD:
+        case KPROF_ENV: return kprof_read_env(family, out, cap);
+        case KPROF_GEMM: return kprof_read(GEMM_PROF_TAG >= 0 || SPLIT_PROF, g_gemm_prof, out, cap);
+        case KPROF_SPLIT: return kprof_read(SPLIT_PROF, g_split_prof, out, cap);
+        case KPROF_RING: return kprof_read(RING_PROF_TAG >= 0, g_ring_prof, out, cap);
+        case KPROF_TABLE: return kprof_read(TABLE_PROF, g_table_prof, out, cap);
+        case KPROF_ATT: return kprof_read(ATT_PROF_MODE >= 0, g_att_prof, out, cap);
+        case KPROF_FIN: return kprof_read(FIN_PROF, g_fin_prof, out, cap);
+    }
+    return -1;
 }
-
-#ifdef MEL_RING_PROF
-// tuning builds only (-DMEL_RING_PROF=<tag>): read and reset the ring kernel's in-kernel cycle counters (tools/ring_prof.py)
-void mel_debug_ring_prof(unsigned long long* out8) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_ring_prof), 8 * sizeof(unsigned long long));
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ring_prof), z, sizeof(z));
-}
-#endif
-#ifdef MEL_GEMM_PROF
-// tuning builds only: read and reset the one-role persistent kernel's cycle counters (tools/gemm_prof.py)
-void mel_debug_gemm_prof(unsigned long long* out8) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_gemm_prof), 8 * sizeof(unsigned long long));
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), z, sizeof(z));
-}
-#endif
-#ifdef MEL_TABLE_PROF
-// tuning builds only: read and reset the table work items' cycle counters (tools/table_prof.py)
-void mel_debug_table_prof(unsigned long long* out8) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_table_prof), 8 * sizeof(unsigned long long));
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_table_prof), z, sizeof(z));
-}
-#endif
-#ifdef MEL_SPLIT_PROF
-void mel_debug_split_prof(unsigned long long* out16) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_split_prof), 16 * sizeof(unsigned long long));
-    unsigned long long z[16] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_prof), z, sizeof(z));
-}
-#endif
-#ifdef MEL_ATT_PROF
-// tuning builds only: read and reset the attention rows kernel's cycle counters (tools/att_prof.py)
-void mel_debug_att_prof(unsigned long long* out8) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_att_prof), 8 * sizeof(unsigned long long));
-    unsigned long long z[8] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_att_prof), z, sizeof(z));
-}
-#endif
 size_t mel_abi_sizeof(int32_t which) {
     switch (which) {
         case 0: return sizeof(mel_linear);

@@ -75,11 +75,14 @@ __device__ __forceinline__ void wait_lds_done() {
 }
 
 #ifdef MEL_RING_PROF
-// Tuning builds (-DMEL_RING_PROF=<TAG>): cycles a consumer wave 0 of the launches tagged TAG spends in [0] MFMA sections, [1] step barriers, [2] epilogues, [3] whole kernel,
-// [4] workgroups counted; loader wave 4: [5] issue (+ epilogue of a finished tile), [6] wait_landed, [7] barrier
-__device__ unsigned long long g_ring_prof[8];
-#define RING_T() __builtin_readcyclecounter()
+constexpr int RING_PROF_TAG = MEL_RING_PROF;
+#else
+constexpr int RING_PROF_TAG = -1;      // no launch carries it
 #endif
+// Tuning builds (-DMEL_RING_PROF=<TAG>, kprof.hpp): cycles a consumer wave 0 of the launches tagged TAG spends in [0] MFMA sections,
+// [1] step barriers, [2] epilogues, [3] whole kernel, [4] workgroups counted; loader wave 4: [5] issue (+ epilogue of a finished
+// tile), [6] wait_landed, [7] barrier
+__device__ unsigned long long g_ring_prof[8];
 
 template <int TAG = 0, int BK = GEMM_BK, int WMC = 2>
 __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_PER_CU)) void gemm_f32_ring_kernel(GemmBatch batch) {
@@ -202,26 +205,15 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
         wait_landed(1);
         __builtin_amdgcn_s_barrier();          // B(-2): steps 0 and 1 are in their stages
         __builtin_amdgcn_s_barrier();          // B(-1): the consumers hold step 0's fragments
-#ifdef MEL_RING_PROF
-        unsigned long long li = 0, lw_ = 0, lb = 0;
-#endif
+        KLaps<TAG == RING_PROF_TAG, 8> prof;
         for (int g = 0; g < steps_total; ++g) {
-#ifdef MEL_RING_PROF
-            const unsigned long long t0 = RING_T();
-#endif
+            prof.mark();
             issue();                           // step g + 4 -> the stage of step g (in registers since B(g-1))
-#ifdef MEL_RING_PROF
-            const unsigned long long t1 = RING_T();
-#endif
+            prof.lap(5);
             if (g + 2 < steps_total) wait_landed(g + 2);
-#ifdef MEL_RING_PROF
-            const unsigned long long t2 = RING_T();
-#endif
+            prof.lap(6);
             __builtin_amdgcn_s_barrier();      // B(g)
-#ifdef MEL_RING_PROF
-            const unsigned long long t3 = RING_T();
-            li += t1 - t0, lw_ += t2 - t1, lb += t3 - t2;
-#endif
+            prof.lap(7);
             if (++ckt == cc.KT) {              // step g completed a tile: its accumulators are in outbuf (written before B(g))
                 write_out();                   // done before this wave reaches B(g+1); the consumers' next hand-over is >= 2 steps away
                 ct = next_valid(ct + stride);
@@ -229,11 +221,7 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
                 if (ct < total) cc = tile_of(ct);
             }
         }
-#ifdef MEL_RING_PROF
-        if (wid == NC && lane == 0 && TAG == MEL_RING_PROF) {
-            atomicAdd(&g_ring_prof[5], li), atomicAdd(&g_ring_prof[6], lw_), atomicAdd(&g_ring_prof[7], lb);
-        }
-#endif
+        prof.flush(g_ring_prof, wid == NC && lane == 0);
         return;
     }
 
@@ -259,28 +247,21 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#ifdef MEL_RING_PROF
-    unsigned long long cm_ = 0, cb = 0, ce = 0;
-    const unsigned long long tk0 = RING_T();
-#endif
+    KLaps<TAG == RING_PROF_TAG, 8> prof;
+    const auto kernel_start = prof.mark();
     f32x4 fa[2][NQ], fb[2][NQ];                // fragments of the step being multiplied / of the next one
     __builtin_amdgcn_s_barrier();              // B(-2)
     read_frags(0, fa[0], fb[0]);
     wait_lds_done();
     __builtin_amdgcn_s_barrier();              // B(-1)
     auto step = [&](int g, f32x4 (&ca)[NQ], f32x4 (&cbf)[NQ], f32x4 (&na)[NQ], f32x4 (&nb)[NQ]) {
-#ifdef MEL_RING_PROF
-        const unsigned long long t0 = RING_T();
-#endif
+        prof.mark();
         if (g + 1 < steps_total) read_frags(g + 1, na, nb);       // landed before B(g-1); overlaps the MFMAs below
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[q][kk], cbf[q][kk], acc, 0, 0, 0);
-#ifdef MEL_RING_PROF
-        asm volatile("s_nop 0" ::"v"(acc[0]));    // the MFMA chain has retired
-        const unsigned long long t1 = RING_T();
-#endif
+        prof.lap(0, acc[0]);                   // the MFMA chain has retired
         if (++kt == c.KT) {                    // tile complete: hand the accumulator block to the loaders
             // (C/D layout: col = lane & 31, row = (e & 3) + 8*(e >> 2) + 4*h)
 #pragma unroll
@@ -292,15 +273,10 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
             kt = 0;
             if (t < total) c = tile_of(t);
         }
-#ifdef MEL_RING_PROF
-        const unsigned long long t2 = RING_T();
-#endif
+        prof.lap(2);
         wait_lds_done();                       // the next step's fragments are in registers, the hand-over is written
         __builtin_amdgcn_s_barrier();          // B(g)
-#ifdef MEL_RING_PROF
-        const unsigned long long t3 = RING_T();
-        cm_ += t1 - t0, ce += t2 - t1, cb += t3 - t2;
-#endif
+        prof.lap(1);
     };
     int g = 0;
     for (; g + 1 < steps_total; g += 2) {
@@ -308,12 +284,9 @@ __global__ __launch_bounds__((RingCfg<BK, WMC>::THREADS), (RingCfg<BK, WMC>::WG_
         step(g + 1, fa[1], fb[1], fa[0], fb[0]);
     }
     if (g < steps_total) step(g, fa[0], fb[0], fa[1], fb[1]);
-#ifdef MEL_RING_PROF
-    if (wid == 0 && lane == 0 && TAG == MEL_RING_PROF) {
-        atomicAdd(&g_ring_prof[0], cm_), atomicAdd(&g_ring_prof[1], cb), atomicAdd(&g_ring_prof[2], ce);
-        atomicAdd(&g_ring_prof[3], RING_T() - tk0), atomicAdd(&g_ring_prof[4], 1ull);
-    }
-#endif
+    prof.since(3, kernel_start);
+    prof.add(4, 1);
+    prof.flush(g_ring_prof, wid == 0 && lane == 0);
 }
 
 // split-K finish: Y = act(scale * (P_0 + P_1 + ... in plane order) + bias) over the row range the launch covered; the

@@ -241,8 +241,15 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(GemmBatch batch) {
 // stream of K steps across the workgroup's work items with the register prefetch two steps ahead; PLAIN mode only.
 // Split-K (GemmArgs::ksplit, ordered as gemm_walk.hpp says): work item = (tile, K chunk), raw products to plane ks.
 #ifdef MEL_SPLIT_PROF
-__device__ unsigned long long g_split_prof[16];      // issue-time stamps inside a K step (tools/split_prof.py)
+constexpr bool SPLIT_PROF = true;
+#else
+constexpr bool SPLIT_PROF = false;
 #endif
+// Tuning builds (-DMEL_GEMM_PROF=99 -DMEL_SPLIT_PROF, kprof.hpp, tools/split_prof.py): cycles of wave 0 of every workgroup of
+// gemm_split_big_kernel, in g_gemm_prof: [0] stream bookkeeping, [1] fragment reads + MFMAs with fill / prefetch between them,
+// [2] LDS writes landing, [3] barrier, [4] epilogue, [5] kernel, [6] workgroups, [7] K steps; and here the time between the
+// issue-time stamps inside a K step: [0] the 12 fragment reads, [1 + 2k] MFMA group k, [2 + 2k] the piece behind group k
+__device__ unsigned long long g_split_prof[16];
 constexpr int GEMS2_ROW = 7;                 // 16-byte chunks per LDS row: 3 planes x 2 chunks + 1 pad
 constexpr int GEMS2_BK = 16;
 
@@ -380,16 +387,11 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     // one K step: MFMAs on `stage`, then Ra (step s+1) -> the other stage, barrier, then Ra <- loads of step s+3
-#ifdef MEL_SPLIT_PROF
-    unsigned long long pm = 0, pw = 0, pb = 0, pi_ = 0, pe = 0, fine[13] = {0};
-    const unsigned long long pk0 = GEMM_T();
-#endif
+    KLaps<SPLIT_PROF, 8> prof;
+    KLaps<SPLIT_PROF, 13> fine;
+    const auto kernel_start = prof.mark();
     auto step = [&](Regs& Ra) {
-#ifdef MEL_SPLIT_PROF
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long q0 = GEMM_T();
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        const auto step_start = prof.mark_fenced();
         const u32x4* cst = lds + stage * BUF;
         bf16x8 a[2][3], b[2][3];
 #pragma unroll
@@ -407,12 +409,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
         // Ra (step s+1) is split and written to the other stage behind groups 0-2, and as soon as its registers are free
         // they are reloaded with step s+3 behind groups 3-4.
         constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
-#ifdef MEL_SPLIT_PROF
-        unsigned long long ts[13];
-        __builtin_amdgcn_sched_barrier(0);
-        ts[0] = GEMM_T();                      // the 12 fragment reads are issued
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        fine.since_fenced(0, step_start);      // the 12 fragment reads are issued
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
 #pragma unroll
@@ -421,45 +418,23 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[k]], b[j][PB[k]], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef MEL_SPLIT_PROF
-            ts[1 + 2 * k] = GEMM_T();          // MFMA group k is issued
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            fine.lap_fenced(1 + 2 * k);        // MFMA group k is issued
             if (k == 0) fill_a(stage ^ 1, Ra, 0);
             if (k == 1) fill_a(stage ^ 1, Ra, 1);
             if (k == 2) fill_w(stage ^ 1, Ra);
             if (k == 3) issue_a(Ra);
             if (k == 4) issue_w(Ra);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef MEL_SPLIT_PROF
-            ts[2 + 2 * k] = GEMM_T();          // the piece behind group k is issued
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            fine.lap_fenced(2 + 2 * k);        // the piece behind group k is issued
         }
-#ifdef MEL_SPLIT_PROF
-        fine[0] += ts[0] - q0;
-#pragma unroll
-        for (int k = 1; k < 13; ++k) fine[k] += ts[k] - ts[k - 1];
-#endif
-#ifdef MEL_SPLIT_PROF
-        asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[1][1][0]));      // the MFMA chains have retired
-        const unsigned long long q1 = GEMM_T();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const unsigned long long q2 = GEMM_T();
-#endif
+        prof.lap(1, acc[0][0][0], acc[1][1][0]);              // the MFMA chains have retired
+        prof.wait_lds();
+        prof.lap(2);
         __syncthreads();
-#ifdef MEL_SPLIT_PROF
-        const unsigned long long q3 = GEMM_T();
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        prof.lap_fenced(3);
         stage ^= 1;
         advance();
-#ifdef MEL_SPLIT_PROF
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long q4 = GEMM_T();
-        __builtin_amdgcn_sched_barrier(0);
-        pm += q1 - q0, pw += q2 - q1, pb += q3 - q2, pi_ += q4 - q3;
-#endif
+        prof.lap_fenced(0);
         if (++ckt == cm.KT) {                  // the work item is complete
             const GemmArgs& g = batch.p[cm.pi];
             if (g.ksplit > 1) {                // raw partial products into this chunk's fp32 plane
@@ -491,26 +466,18 @@ __global__ __launch_bounds__(256, 2) void gemm_split_big_kernel(GemmBatch batch)
             cm = nm, ckt = 0;
             if (!nm_valid) cm.KT = 1 << 30;    // (the padding step of an odd stream ends no work item)
             nm_valid = false;
-#ifdef MEL_SPLIT_PROF
-            pe += GEMM_T() - q4;
-#endif
+            prof.lap(4);
         }
     };
     for (int it = 0; it < (nsteps + 1) >> 1; ++it) {       // counted loop over pairs of steps (see gemm_split_kernel)
         step(R1);
         step(R0);
     }
-#ifdef MEL_SPLIT_PROF
-    // tuning builds (-DMEL_GEMM_PROF=99 -DMEL_SPLIT_PROF, tools/split_prof.py): cycles of wave 0 of every workgroup in [0] stream
-    // bookkeeping, [1] fragment reads + MFMAs with fill / prefetch between them, [2] LDS writes landing, [3] barrier, [4] epilogue, [5] kernel
-    if (tid == 0) {
-        atomicAdd(&g_gemm_prof[0], pi_), atomicAdd(&g_gemm_prof[1], pm), atomicAdd(&g_gemm_prof[2], pw);
-        atomicAdd(&g_gemm_prof[3], pb), atomicAdd(&g_gemm_prof[4], pe), atomicAdd(&g_gemm_prof[5], GEMM_T() - pk0);
-        atomicAdd(&g_gemm_prof[6], 1ull), atomicAdd(&g_gemm_prof[7], (unsigned long long)nsteps);
-#pragma unroll
-        for (int k = 0; k < 13; ++k) atomicAdd(&g_split_prof[k], fine[k]);
-    }
-#endif
+    prof.since(5, kernel_start);
+    prof.add(6, 1);
+    prof.add(7, (unsigned long long)nsteps);
+    prof.flush(g_gemm_prof, tid == 0);
+    fine.flush(g_split_prof, tid == 0);
 }
 
 // Round 3 built three more forms of this kernel - specialised wavefronts (4 MFMA waves + one or two teams of loader waves, 3- /

@@ -56,15 +56,14 @@ struct TableArgs {
 static inline int table_items(const TableArgs& a) { return ((a.T + TBL_BM - 1) / TBL_BM) * (a.N / TBL_BN); }
 
 #ifdef MEL_TABLE_PROF
-// Tuning builds (-DMEL_TABLE_PROF): cycles wave 0 of every table work item spends [0] up to the finished layer-0 block,
+constexpr bool TABLE_PROF = true;
+#else
+constexpr bool TABLE_PROF = false;
+#endif
+// Tuning builds (-DMEL_TABLE_PROF, kprof.hpp): cycles wave 0 of every table work item spends [0] up to the finished layer-0 block,
 // [1] in layer 1's products, [2] storing its rows, [3] in conv1's products, [4] in conv1's epilogue, [5] in all, [6] items
 // counted (tools/table_prof.py)
 __device__ unsigned long long g_table_prof[8];
-#define TBL_T() __builtin_readcyclecounter()
-#define TBL_STAMP(i) do { const unsigned long long t_ = TBL_T(); tp[i] = t_ - tl; tl = t_; } while (0)
-#else
-#define TBL_STAMP(i)
-#endif
 
 // Between the lanes that write a wavefront's own LDS stage and the lanes that read it (and back, before the next slices
 // overwrite it): the LDS operations of one wavefront execute in order, so no instruction is needed - a wavefront-scope
@@ -84,10 +83,8 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
     const int T = a.T;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
-#ifdef MEL_TABLE_PROF
-    unsigned long long tp[5], tl = TBL_T();
-    const unsigned long long t00 = tl;
-#endif
+    KLaps<TABLE_PROF, 8> prof;
+    const auto item_start = prof.mark();
     float* ablk = lds;
     float* enc = lds + TBL_BM * TBL_A_STRIDE;         // layer-0 weights as [128][9]
 
@@ -157,7 +154,7 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
         }
     }
     __syncthreads();
-    TBL_STAMP(0);
+    prof.lap(0);
 
     // layer 1: 32 x 128, one 32 x 32 block per wavefront
     const float* afrag = ablk + r * TBL_A_STRIDE + 4 * h;
@@ -184,7 +181,7 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
     for (int sg = 2; sg < 4; ++sg)
 #pragma unroll
         for (int g = 0; g < 8; ++g) wcr[sg][g] = *reinterpret_cast<const f32x4*>(wc_src[g] + 32 * sg);
-    TBL_STAMP(1);
+    prof.lap(1);
     __syncthreads();                    // every wavefront has read layer 0's rows: the finished rows replace them
     {
         const int n = wid * 32 + r;
@@ -204,7 +201,7 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
         }
     }
     __syncthreads();
-    TBL_STAMP(2);
+    prof.lap(2);
 
     // conv1: 32 x 256, 32 x 64 per wavefront
     f32x16 acc[2];
@@ -230,7 +227,7 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
         }
         table_stage_handoff();
     }
-    TBL_STAMP(3);
+    prof.lap(3);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = cg * TBL_BN + wid * 64 + j * 32 + r;
@@ -244,14 +241,11 @@ __device__ __forceinline__ void table_fused_tile(const TableArgs& a, const int b
             if (m < T) col[(size_t)m * ldy] = acc[j][e] + bias;
         }
     }
-#ifdef MEL_TABLE_PROF
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TBL_STAMP(4);
-    if (tid == 0) {
-        for (int i = 0; i < 5; ++i) atomicAdd(&g_table_prof[i], tp[i]);
-        atomicAdd(&g_table_prof[5], TBL_T() - t00), atomicAdd(&g_table_prof[6], 1ull);
-    }
-#endif
+    prof.wait_vmem();
+    prof.lap(4);
+    prof.since(5, item_start);
+    prof.add(6, 1);
+    prof.flush(g_table_prof, tid == 0);
 }
 
 // the table alone (mel_feature_tables_fused)

@@ -1,21 +1,16 @@
 """Tuning aid: in-kernel cycle breakdown of gemm_f32_ring_kernel over a few round steps.
 Build with MEL_HIPCC_FLAGS="-DMEL_RING_PROF=3" (the heads' first layer, the one launch the ring kernel serves)."""
-import ctypes as C, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from melissa_amd import _lib
+import kprof
 net, venv, loop = bench.build_workload(torch.device("cuda", 0), 0, 1024, 50, "l_dgn", "round", False, 1)
-lib = _lib.load()
-fn = lib.mel_debug_ring_prof
-fn.argtypes = [C.c_void_p]
-buf = (C.c_ulonglong * 8)()
 loop.run(20)
-fn(buf)
+kprof.read("ring")
 N = 20
 loop.run(N)
-fn(buf)
-v = list(buf)
+v = kprof.read("ring")
 wgs = v[4]
 print("workgroups counted", wgs, "per step", wgs / N)
 names = ["consumer MFMA section", "consumer step barrier", "consumer epilogue", "consumer whole kernel", "-", "loader issue", "loader wait_landed", "loader barrier"]
