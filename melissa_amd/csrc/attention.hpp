@@ -49,6 +49,7 @@ struct AttArgs {
     // node-feature table mode (plan_masks.hpp): xl / xr / h0 are TABLES indexed by a node's tuple id fid[b*N + i] instead of
     // row lists indexed by packed position (null = row lists)
     const int32_t* fid;
+    int legacy_walk;            // MEL_FWD_ATT_LEGACY_WALK / MEL_ATT_LEGACY_WALK: the per-step source selection (ATT_WALK_LEGACY)
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -137,8 +138,10 @@ __device__ __forceinline__ void store_row(float* base, size_t idx, const Vec<VPL
 
 // sum over the lanes of one head (lanes_per_head adjacent lanes).  The common case (16 lanes: C = 128,
 // 8 channels per lane) is four DPP moves inside a 16-lane row; anything else falls back to shuffles.
+// LPH = 16: known at compile time (no branch, no shuffle loop in the caller's step); 0: decided per call.
+template <int LPH = 0>
 __device__ __forceinline__ float head_sum(float s, int lanes_per_head) {
-    if (lanes_per_head == 16) {
+    if (LPH == 16 || lanes_per_head == 16) {
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x141, 0xF, 0xF, true));  // row_half_mirror
@@ -160,11 +163,101 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 // KIND = MEL_CONV_TRANSFORMER: e = (q[i] . k[j]) / sqrt(C), k | v side by side, out = sum alpha v[j]
 // my_fid: table mode - the tuple ids of this lane's nodes (node lane + 64 h of the target's env); a source row is then the
 // table row of the source's tuple (one v_readlane) instead of its packed position in the row list.
-template <int VPL, int KIND, bool BF, int W, int G>
+//
+// How a target's sources are walked (ATT_WALK_*).  The arithmetic of a step (attend_step) and the source order - ascending
+// node id, G per step - are the same in every form, so the output bits are too.
+//   LEGACY   every step picks its G sources off the 64-bit set (ffbl chains, readfirstlane) and decides table mode and the
+//            lanes per head at run time: the walk before the list forms, kept selectable for one release
+//            (MEL_FWD_ATT_LEGACY_WALK / MEL_ATT_LEGACY_WALK)
+//   the list forms build the target's source list ONCE - lane k holds the row index of the k-th source - and a step takes its G
+//   row indices from that register with v_readlane: no set arithmetic and no launch-uniform branch inside a step
+//   GENERIC  table mode and the lanes per head decided at run time (any shape)
+//   LIST_16 / TABLE_16  row-list / table mode with 16 lanes per head, both known at compile time (the headline shapes)
+enum { ATT_WALK_LEGACY = 0, ATT_WALK_GENERIC = 1, ATT_WALK_LIST_16 = 2, ATT_WALK_TABLE_16 = 3 };
+
+template <int FORM>
+__device__ __forceinline__ bool att_table_mode(const AttArgs& a) {
+    if constexpr (FORM == ATT_WALK_TABLE_16) return true;
+    else if constexpr (FORM == ATT_WALK_LIST_16) return false;
+    else return a.fid != nullptr;
+}
+
+// start of source row `srow` (wave-uniform): the row loads then take a scalar base and this lane's constant offset
+template <bool BF>
+__device__ __forceinline__ const float* source_row(const float* base, int srow, int ld) {
+    typedef const char __attribute__((address_space(1))) * global_bytes;
+    global_bytes p = (global_bytes)base + (size_t)srow * ld * (BF ? 2 : 4);
+    // the address stays in its SGPR pair up to the load (scalar base + 32-bit lane offset): without this the lane's offset
+    // is folded into the base ahead of the loop and every row costs a 64-bit vector add and an address register pair
+    asm("" : "+s"(p));
+    return (const float*)p;
+}
+
+// one online-softmax step over the G source rows xl (xv: their value halves, TransformerConv); off slots weigh nothing
+template <int VPL, int KIND, int G, int LPH>
+__device__ __forceinline__ void attend_step(const AttArgs& a, const Vec<VPL>& xr, const Vec<VPL>& att, const Vec<VPL> (&xl)[G],
+                                            const Vec<VPL> (&xv)[G], const bool (&on)[G], float& m, float& l, Vec<VPL>& acc) {
+    float sc_[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        float t = 0.f;
+        if constexpr (KIND == MEL_CONV_GATV2 && VPL % 2 == 0) {
+            // leaky_relu(negative_slope=0.2) as max(z, 0.2 z): same value for every finite z and one op
+            // fewer than compare + select; channel pairs so that add / scale / fma issue as v_pk_*_f32
+            f32x2 t2 = {0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < VPL; i += 2) {
+                const f32x2 z = f32x2{xr.v[i], xr.v[i + 1]} + f32x2{xl[k].v[i], xl[k].v[i + 1]};
+                const f32x2 zs = z * 0.2f;
+                const f32x2 zm = {fmaxf(z.x, zs.x), fmaxf(z.y, zs.y)};
+                t2 = __builtin_elementwise_fma(f32x2{att.v[i], att.v[i + 1]}, zm, t2);
+            }
+            t = t2.x + t2.y;
+        } else if constexpr (KIND == MEL_CONV_GATV2) {
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) {
+                const float z = xr.v[i] + xl[k].v[i];
+                t = fmaf(att.v[i], fmaxf(z, 0.2f * z), t);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VPL; ++i) t = fmaf(xr.v[i], xl[k].v[i], t);
+        }
+        sc_[k] = t;
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        sc_[k] = head_sum<LPH>(sc_[k], a.lanes_per_head);
+        if constexpr (KIND == MEL_CONV_TRANSFORMER) sc_[k] *= a.score_scale;
+        if (!on[k]) sc_[k] = -INFINITY;
+    }
+    float mn = m;
+#pragma unroll
+    for (int k = 0; k < G; ++k) mn = fmaxf(mn, sc_[k]);
+    // e^x as v_exp_f32(x log2 e): ~1e-6 relative on softmax weights that are later normalised (the libm
+    // expansion was a quarter of this kernel's VALU work, and the kernel is VALU / latency bound)
+    const float rs = fast_exp(m - mn);       // slot 0 is always on, so mn is finite
+    float pe[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) pe[k] = fast_exp(sc_[k] - mn);   // exp(-inf) = 0 for the off slots
+    float ps = 0.f;
+#pragma unroll
+    for (int k = 0; k < G; ++k) ps += pe[k];
+    l = l * rs + ps;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        float t = acc.v[i] * rs;
+#pragma unroll
+        for (int k = 0; k < G; ++k) t = fmaf(pe[k], (KIND == MEL_CONV_TRANSFORMER ? xv[k].v[i] : xl[k].v[i]), t);
+        acc.v[i] = t;
+    }
+    m = mn;
+}
+
+template <int VPL, int KIND, bool BF, int W, int G, int FORM>
 __device__ __forceinline__ Vec<VPL> attend_target(const AttArgs& a, size_t xr_row, NodeSet<W> sources,
                                                   const NodeSet<W>& smask, int soff, const Vec<VPL>& att,
                                                   const Vec<VPL>& bias, int lane, const int (&my_fid)[W]) {
-    const bool table = a.fid != nullptr;
     constexpr int HC = 64 * VPL;
     // G = sources per online-softmax step.  Row kernels: 2 - with 4 the kernel needs 112 VGPRs (four waves per SIMD), with 2 it
     // fits 96 (five): conv1 attention 24.3 -> 22.8 us, conv2 attention 13.4 -> 13.0 us, step 0.2180 -> 0.2142 ms (two A/B
@@ -174,78 +267,71 @@ __device__ __forceinline__ Vec<VPL> attend_target(const AttArgs& a, size_t xr_ro
     Vec<VPL> acc;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) acc.v[i] = 0.f;
-    while (ns_any(sources)) {                    // TransformerConv adds no self-loop: a target may be isolated
-        size_t row[G];                           // element index of this lane's slice of the source row
-        bool on[G];
+    if constexpr (FORM == ATT_WALK_LEGACY) {
+        const bool table = a.fid != nullptr;
+        while (ns_any(sources)) {                    // TransformerConv adds no self-loop: a target may be isolated
+            size_t row[G];                           // element index of this lane's slice of the source row
+            bool on[G];
 #pragma unroll
-        for (int k = 0; k < G; ++k) {
-            on[k] = ns_any(sources);
-            const int j = on[k] ? ns_lowest(sources) : 0;
-            ns_clear_lowest(sources);            // empty stays empty
-            const int srow = table ? node_i32<W>(my_fid, j) : soff + (on[k] ? ns_rank_below(smask, j) : 0);
-            row[k] = (size_t)srow * a.ld_l + lane * VPL;                     // off slots re-read a valid row
+            for (int k = 0; k < G; ++k) {
+                on[k] = ns_any(sources);
+                const int j = on[k] ? ns_lowest(sources) : 0;
+                ns_clear_lowest(sources);            // empty stays empty
+                const int srow = table ? node_i32<W>(my_fid, j) : soff + (on[k] ? ns_rank_below(smask, j) : 0);
+                row[k] = (size_t)srow * a.ld_l + lane * VPL;                     // off slots re-read a valid row
+            }
+            Vec<VPL> xl[G], xv[G];
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                xl[k] = load_row<VPL, BF>(a.xl, row[k]);
+                if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(a.xl, row[k] + HC);
+            }
+            attend_step<VPL, KIND, G, 0>(a, xr, att, xl, xv, on, m, l, acc);
         }
-        Vec<VPL> xl[G], xv[G];
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            xl[k] = load_row<VPL, BF>(a.xl, row[k]);
-            if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(a.xl, row[k] + HC);
-        }
-        float sc_[G];
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            float t = 0.f;
-            if constexpr (KIND == MEL_CONV_GATV2 && VPL % 2 == 0) {
-                // leaky_relu(negative_slope=0.2) as max(z, 0.2 z): same value for every finite z and one op
-                // fewer than compare + select; channel pairs so that add / scale / fma issue as v_pk_*_f32
-                f32x2 t2 = {0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < VPL; i += 2) {
-                    const f32x2 z = f32x2{xr.v[i], xr.v[i + 1]} + f32x2{xl[k].v[i], xl[k].v[i + 1]};
-                    const f32x2 zs = z * 0.2f;
-                    const f32x2 zm = {fmaxf(z.x, zs.x), fmaxf(z.y, zs.y)};
-                    t2 = __builtin_elementwise_fma(f32x2{att.v[i], att.v[i + 1]}, zm, t2);
-                }
-                t = t2.x + t2.y;
-            } else if constexpr (KIND == MEL_CONV_GATV2) {
-#pragma unroll
-                for (int i = 0; i < VPL; ++i) {
-                    const float z = xr.v[i] + xl[k].v[i];
-                    t = fmaf(att.v[i], fmaxf(z, 0.2f * z), t);
+    } else {
+        constexpr int LPH = FORM == ATT_WALK_GENERIC ? 0 : 16;
+        constexpr int CHUNK = 64 - 64 % G;           // sources per list: whole steps, one lane each (the neighbour cap keeps a
+                                                     // target at 34 sources, so this loop runs once; it is here for the bound)
+        NodeSet<W> left = ns_uniform(sources);       // SGPRs: the list is built by scalar instructions
+        int count = ns_count(left);
+        while (count > 0) {                          // TransformerConv adds no self-loop: a target may be isolated
+            const int nl = min(count, CHUNK);
+            // lane k: node id of the k-th source in ascending order; the lanes past the list keep node 0, whose row is
+            // the valid row an off slot re-reads
+            int node = 0;
+            for (int k = 0; k < nl; ++k) {
+                node = lane == k ? ns_lowest(left) : node;       // scalar walk of the set, one compare + select per source
+                ns_clear_lowest(left);
+            }
+            int rowv;                                // ... and the row index of that node: its tuple id, or its packed position
+            if (att_table_mode<FORM>(a)) {
+                if constexpr (W == 1) rowv = __builtin_amdgcn_ds_bpermute(node << 2, my_fid[0]);
+                else {
+                    const int lo = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[0]);
+                    const int hi = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[1]);
+                    rowv = node < 64 ? lo : hi;
                 }
             } else {
-#pragma unroll
-                for (int i = 0; i < VPL; ++i) t = fmaf(xr.v[i], xl[k].v[i], t);
+                rowv = soff + ns_rank_below(smask, node);
             }
-            sc_[k] = t;
+            for (int s0 = 0; s0 < nl; s0 += G) {
+                Vec<VPL> xl[G], xv[G];
+                bool on[G];
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    on[k] = s0 + k < nl;             // slot 0 is always on
+                    const float* src = source_row<BF>(a.xl, __builtin_amdgcn_readlane(rowv, s0 + k), a.ld_l);
+                    xl[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL));
+                    if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL + HC));
+                }
+                // every row load of the step is in flight before its arithmetic starts (left alone, the scheduler sinks the
+                // second source's loads below the first source's score: one memory latency after the other).  Not for bf16 rows:
+                // their loads are issued together anyway, and holding both rows unpacked costs 16 VGPRs and a wave per SIMD
+                if constexpr (!BF) __builtin_amdgcn_sched_barrier(0);
+                attend_step<VPL, KIND, G, LPH>(a, xr, att, xl, xv, on, m, l, acc);
+            }
+            count -= nl;
         }
-#pragma unroll
-        for (int k = 0; k < G; ++k) {
-            sc_[k] = head_sum(sc_[k], a.lanes_per_head);
-            if constexpr (KIND == MEL_CONV_TRANSFORMER) sc_[k] *= a.score_scale;
-            if (!on[k]) sc_[k] = -INFINITY;
-        }
-        float mn = m;
-#pragma unroll
-        for (int k = 0; k < G; ++k) mn = fmaxf(mn, sc_[k]);
-        // e^x as v_exp_f32(x log2 e): ~1e-6 relative on softmax weights that are later normalised (the libm
-        // expansion was a quarter of this kernel's VALU work, and the kernel is VALU / latency bound)
-        const float rs = fast_exp(m - mn);       // slot 0 is always on, so mn is finite
-        float pe[G];
-#pragma unroll
-        for (int k = 0; k < G; ++k) pe[k] = fast_exp(sc_[k] - mn);   // exp(-inf) = 0 for the off slots
-        float ps = 0.f;
-#pragma unroll
-        for (int k = 0; k < G; ++k) ps += pe[k];
-        l = l * rs + ps;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) {
-            float t = acc.v[i] * rs;
-#pragma unroll
-            for (int k = 0; k < G; ++k) t = fmaf(pe[k], (KIND == MEL_CONV_TRANSFORMER ? xv[k].v[i] : xl[k].v[i]), t);
-            acc.v[i] = t;
-        }
-        m = mn;
     }
     const float inv = __builtin_amdgcn_rcpf(l + 1e-16f);
     Vec<VPL> out;
@@ -324,8 +410,9 @@ __device__ unsigned long long g_att_prof[8];
 #ifndef MEL_ATT_GP
 #define MEL_ATT_GP 2     // ... of the HL-DGN pool kernel (4 -> 2: pool attention 39.9 -> 33.5 us, HL-DGN 512 envs 24.4 -> 26.1 M/s)
 #endif
-template <int VPL, int MODE, int KIND, bool BF, int W>
+template <int VPL, int MODE, int KIND, bool BF, int W, int FORM>
 __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttArgs a) {
+    const bool table = MODE == ATT_ROWS && att_table_mode<FORM>(a);
     KLaps<MODE == ATT_PROF_MODE && !BF, 8> prof;
     const auto wave_start = prof.mark();
     const int lane = lane_id();
@@ -343,7 +430,9 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
     const int vblock = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     const int rows_pad = ((rows + 4 * (int)gridDim.x - 1) / (4 * (int)gridDim.x)) * (4 * (int)gridDim.x);
     const int span = rows_pad >> 3;              // rows each XCD owns (multiple of 4 * per_xcd)
-    for (int i = (vblock % per_xcd) * 4 + (threadIdx.x >> 6); i < span; i += per_xcd * 4) {
+    // the list forms keep the wave's number, and with it the row index and everything addressed by it, in SGPRs
+    const int wave = FORM == ATT_WALK_LEGACY ? (int)(threadIdx.x >> 6) : uniform_i32(threadIdx.x >> 6);
+    for (int i = (vblock % per_xcd) * 4 + wave; i < span; i += per_xcd * 4) {
         const int r = (blockIdx.x & 7) * span + i;
         if (r >= rows) continue;
         prof.mark();
@@ -352,11 +441,11 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
         int my_fid[W];
         MEL_W_FOR(h) my_fid[h] = 0;
         size_t xr_row = (size_t)r;
-        if (MODE == ATT_ROWS && a.fid) {             // table mode: tuple ids of the target's env (one dependent load)
+        if (table) {                                 // table mode: tuple ids of the target's env (one dependent load)
             MEL_W_FOR(h) my_fid[h] = lane + 64 * h < a.n ? a.fid[(size_t)d.env * a.n + lane + 64 * h] : 0;
             xr_row = (size_t)node_i32<W>(my_fid, d.node);
         }
-        const Vec<VPL> o = attend_target<VPL, KIND, BF, W, MEL_ATT_G>(a, xr_row, d.sources, d.smask, d.soff, att, bias, lane, my_fid);
+        const Vec<VPL> o = attend_target<VPL, KIND, BF, W, MEL_ATT_G, FORM>(a, xr_row, d.sources, d.smask, d.soff, att, bias, lane, my_fid);
         prof.lap(2, o.v[0]);
         if constexpr (MODE == ATT_SINGLE) {
             store_row<VPL, BF>(a.xcat, (size_t)r * a.ld_cat + a.cat_off + lane * VPL, o);
@@ -377,7 +466,7 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
                 // x_2: the controlling agent's conv1 row BEFORE the decision-maker mask (l_dgn.py:127)
                 store_row<VPL, BF>(a.xcat, cat + a.hidden + lane * VPL, o);
                 // x_1: its encoder row (l_dgn.py:122)
-                const size_t h0 = (size_t)(a.fid ? node_i32<W>(my_fid, d.node) : d.soff + ns_rank_below(d.smask, d.node)) * a.hidden;
+                const size_t h0 = (size_t)(table ? node_i32<W>(my_fid, d.node) : d.soff + ns_rank_below(d.smask, d.node)) * a.hidden;
                 if constexpr (BF) {
                     uint16_t* dst = reinterpret_cast<uint16_t*>(a.xcat) + cat;
                     const uint16_t* src = reinterpret_cast<const uint16_t*>(a.h0) + h0;
@@ -400,8 +489,9 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
 // NW wavefronts per env: at 512 envs per GPU four waves per workgroup leave a CU with 8 resident waves (two workgroups),
 // too few to hide the source-row latency; eight waves (MEL_POOL_NW; six or seven targets each at N = 50) with two source rows
 // per step measure best (sixteen: 33.4 us, twelve: 35.1, eight: 31.6).
-template <int VPL, bool BF, int NW, int W>
+template <int VPL, bool BF, int NW, int W, int FORM>
 __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
+    const bool table = att_table_mode<FORM>(a);
     constexpr int HC = 64 * VPL;
     __shared__ float part[NW][HC];
     const int lane = lane_id();
@@ -414,11 +504,11 @@ __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) pool.v[i] = (a.aggregator == MEL_AGG_MAX) ? -INFINITY : 0.f;
     int my_fid[W];                                                                    // table mode (null: rows b*N + i)
-    MEL_W_FOR(h) my_fid[h] = (a.fid && lane + 64 * h < a.n) ? a.fid[(size_t)b * a.n + lane + 64 * h] : 0;
+    MEL_W_FOR(h) my_fid[h] = (table && lane + 64 * h < a.n) ? a.fid[(size_t)b * a.n + lane + 64 * h] : 0;
     for (int t = wave; t < a.n; t += NW) {
         const NodeSet<W> sources = ns_load<W>(a.adj, (size_t)b * a.n + t) | ns_bit<W>(t);
-        const size_t xr_row = a.fid ? (size_t)node_i32<W>(my_fid, t) : (size_t)(b * a.n + t);
-        const Vec<VPL> o = attend_target<VPL, MEL_CONV_GATV2, BF, W, MEL_ATT_GP>(a, xr_row, sources, full, b * a.n, att, bias, lane, my_fid);
+        const size_t xr_row = table ? (size_t)node_i32<W>(my_fid, t) : (size_t)(b * a.n + t);
+        const Vec<VPL> o = attend_target<VPL, MEL_CONV_GATV2, BF, W, MEL_ATT_GP, FORM>(a, xr_row, sources, full, b * a.n, att, bias, lane, my_fid);
         // hl_dgn.py:105-108: mask out non-decision-makers, then pool over the graph
         const float dm = a.obs[(size_t)b * a.obs_stride + t * a.node_cols + a.node_cols - 1];
 #pragma unroll
@@ -445,29 +535,66 @@ __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
     }
 }
 
-template <int MODE>
-static mel_status launch_attend(const AttArgs& a, int hc, hipStream_t s, const char* what) {
+// The walk form of a launch (ATT_WALK_*).  The compile-time forms exist for 8 channels per lane with 16 lanes per head - hidden
+// size 128 with four heads, which every configuration BASELINE quotes runs at; every other shape takes the generic list walk.
+template <int V, int MODE>
+static int att_walk_form(const AttArgs& a) {
+    if (a.legacy_walk) return ATT_WALK_LEGACY;
+    if (V == 8 && a.lanes_per_head == 16) return (MODE != ATT_SINGLE && a.fid) ? ATT_WALK_TABLE_16 : ATT_WALK_LIST_16;
+    return ATT_WALK_GENERIC;
+}
+
+template <int V, int MODE, int FORM>
+static void launch_attend_form(const AttArgs& a, int grid, hipStream_t s) {
     if constexpr (MODE == ATT_POOL) {
-        switch (hc / 64) {
-#define MEL_POOL_LAUNCH(V)                                                                                         \
-    if (a.n > 64) {             /* graphs of 65 .. 128 nodes: two-word node sets */                               \
-        if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 16, 2>), dim3(a.bs), dim3(1024), 0, s, a);        \
-        else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 16, 2>), dim3(a.bs), dim3(1024), 0, s, a);              \
-    } else if (a.bs >= 2048) {                                                                                    \
-        if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 4, 1>), dim3(a.bs), dim3(256), 0, s, a);  \
-        else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 4, 1>), dim3(a.bs), dim3(256), 0, s, a);        \
-    } else {                                                                                                      \
-        if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, MEL_POOL_NW, 1>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);   \
-        else MEL_LAUNCH((gat_attend_pool_kernel<V, false, MEL_POOL_NW, 1>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);         \
-    }
-            case 2: MEL_POOL_LAUNCH(2) break;
-            case 4: MEL_POOL_LAUNCH(4) break;
-            case 8: MEL_POOL_LAUNCH(8) break;
-            case 16: MEL_POOL_LAUNCH(16) break;
-#undef MEL_POOL_LAUNCH
-            default: return fail(MEL_ERR_UNSUPPORTED, "%s: heads*C = %d not in {128,256,512,1024}", what, hc);
+        if (a.n > 64) {             // graphs of 65 .. 128 nodes: two-word node sets
+            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 16, 2, FORM>), dim3(a.bs), dim3(1024), 0, s, a);
+            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 16, 2, FORM>), dim3(a.bs), dim3(1024), 0, s, a);
+        } else if (a.bs >= 2048) {
+            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 4, 1, FORM>), dim3(a.bs), dim3(256), 0, s, a);
+            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 4, 1, FORM>), dim3(a.bs), dim3(256), 0, s, a);
+        } else {
+            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, MEL_POOL_NW, 1, FORM>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);
+            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, MEL_POOL_NW, 1, FORM>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);
         }
     } else {
+#define MEL_ATT_LAUNCH_W(WW)                                                                                                   \
+    if (a.kind == MEL_CONV_TRANSFORMER && a.bf16)                                                                              \
+        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, true, WW, FORM>), dim3(grid), dim3(256), 0, s, a);   \
+    else if (a.kind == MEL_CONV_TRANSFORMER)                                                                                   \
+        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, false, WW, FORM>), dim3(grid), dim3(256), 0, s, a);  \
+    else if (a.bf16)                                                                                                           \
+        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, true, WW, FORM>), dim3(grid), dim3(256), 0, s, a);         \
+    else                                                                                                                       \
+        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, false, WW, FORM>), dim3(grid), dim3(256), 0, s, a);
+        if (a.n > 64) {
+            MEL_ATT_LAUNCH_W(2)
+        } else {
+            MEL_ATT_LAUNCH_W(1)
+        }
+#undef MEL_ATT_LAUNCH_W
+    }
+}
+
+// V channels per lane: the launch in the walk form of its arguments - only the forms att_walk_form can name are instantiated
+template <int V, int MODE>
+static void launch_attend_v(const AttArgs& a, int grid, hipStream_t s) {
+    switch (att_walk_form<V, MODE>(a)) {
+        case ATT_WALK_LEGACY: launch_attend_form<V, MODE, ATT_WALK_LEGACY>(a, grid, s); break;
+        case ATT_WALK_LIST_16:
+            if constexpr (V == 8) launch_attend_form<V, MODE, ATT_WALK_LIST_16>(a, grid, s);
+            break;
+        case ATT_WALK_TABLE_16:
+            if constexpr (V == 8 && MODE != ATT_SINGLE) launch_attend_form<V, MODE, ATT_WALK_TABLE_16>(a, grid, s);
+            break;
+        default: launch_attend_form<V, MODE, ATT_WALK_GENERIC>(a, grid, s); break;
+    }
+}
+
+template <int MODE>
+static mel_status launch_attend(const AttArgs& a, int hc, hipStream_t s, const char* what) {
+    int grid = 0;                                       // the pool kernel: one workgroup per env
+    if constexpr (MODE != ATT_POOL) {
         long want = ((a.rows_hint > 0 ? a.rows_hint : a.rows_cap) * 5 / 4 + 3) / 4;     // 25 % head-room, loop covers the rest
         if (want > (a.rows_cap + 3) / 4) want = (a.rows_cap + 3) / 4;
         if (want < 256) want = 256;
@@ -477,31 +604,14 @@ static mel_status launch_attend(const AttArgs& a, int hc, hipStream_t s, const c
 #ifdef MEL_ATT2_GRID_CAP
         if (MODE == ATT_SINGLE && want > MEL_ATT2_GRID_CAP) want = MEL_ATT2_GRID_CAP;
 #endif
-        const int grid = (int)((want + 7) & ~7L);       // multiple of 8: block id % 8 = XCD
-#define MEL_ATT_LAUNCH_W(V, WW)                                                                                          \
-    if (a.kind == MEL_CONV_TRANSFORMER && a.bf16)                                                                     \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, true, WW>), dim3(grid), dim3(256), 0, s, a);  \
-    else if (a.kind == MEL_CONV_TRANSFORMER)                                                                          \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, false, WW>), dim3(grid), dim3(256), 0, s, a); \
-    else if (a.bf16)                                                                                                  \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, true, WW>), dim3(grid), dim3(256), 0, s, a);        \
-    else                                                                                                              \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, false, WW>), dim3(grid), dim3(256), 0, s, a);
-#define MEL_ATT_LAUNCH(V)                                                                                             \
-    if (a.n > 64) {                                                                                                   \
-        MEL_ATT_LAUNCH_W(V, 2)                                                                                        \
-    } else {                                                                                                          \
-        MEL_ATT_LAUNCH_W(V, 1)                                                                                        \
+        grid = (int)((want + 7) & ~7L);                 // multiple of 8: block id % 8 = XCD
     }
-        switch (hc / 64) {
-            case 2: MEL_ATT_LAUNCH(2) break;
-            case 4: MEL_ATT_LAUNCH(4) break;
-            case 8: MEL_ATT_LAUNCH(8) break;
-            case 16: MEL_ATT_LAUNCH(16) break;
-            default: return fail(MEL_ERR_UNSUPPORTED, "%s: heads*C = %d not in {128,256,512,1024}", what, hc);
-        }
-#undef MEL_ATT_LAUNCH
-#undef MEL_ATT_LAUNCH_W
+    switch (hc / 64) {
+        case 2: launch_attend_v<2, MODE>(a, grid, s); break;
+        case 4: launch_attend_v<4, MODE>(a, grid, s); break;
+        case 8: launch_attend_v<8, MODE>(a, grid, s); break;
+        case 16: launch_attend_v<16, MODE>(a, grid, s); break;
+        default: return fail(MEL_ERR_UNSUPPORTED, "%s: heads*C = %d not in {128,256,512,1024}", what, hc);
     }
     return check_launch(what);
 }

@@ -476,6 +476,8 @@ static FeatureTables carve_tables(const mel_weights* w, int n, void* buf, size_t
     if (bytes) *bytes = c.off;
     return t;
 }
+// the attention launches of this call in the former source walk: the caller's flag, or MEL_ATT_LEGACY_WALK for the process
+static int att_legacy_walk(const mel_weights* w) { return (w->flags & MEL_FWD_ATT_LEGACY_WALK) || gemm_tuning().att_legacy_walk; }
 // The shapes table_fused_tile is built for (gemm_table.hpp): GATv2 L-DGN on the exact-fp32 instruction - MEL_PREC_F32, and
 // MEL_PREC_F32_AUTO, whose table launches are far too small for the split kernels.  Everything else (the bf16 feature path,
 // MEL_PREC_F32_SPLIT, DGN-R's three source-side matrices, HL-DGN) keeps the two-launch form.
@@ -685,7 +687,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.out = L.h1, a.ldo = hc, a.xcat = L.xcat, a.ld_cat = latent, a.hidden = hidden, a.h0 = ft.h0;
         if (conv2.kernel == GemmKernel::PLANES) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
         a.out_scale = L.plan.dm1;       // the decision-maker mask (l_dgn.py:128) is applied as h1 is stored; x_2 is taken before it
-        a.fid = table ? L.plan.fid : nullptr;
+        a.fid = table ? L.plan.fid : nullptr, a.legacy_walk = att_legacy_walk(w);
         StageScope t(MEL_STAGE_CONV1_ATT, s);
         if (mel_status st = launch_attend<ATT_ROWS>(a, hc, s, "conv1 attention")) return st;
     }
@@ -700,7 +702,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.adj = L.plan.adj;
         a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv2.channels / (hc / 64);
         a.desc = L.plan.desc2, a.rows_dev = nL, a.rows_cap = R, a.rows_hint = hintL;
-        a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc;
+        a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc, a.legacy_walk = att_legacy_walk(w);
         StageScope t(MEL_STAGE_CONV2_ATT, s);
         if (mel_status st = launch_attend<ATT_SINGLE>(a, hc, s, "conv2 attention")) return st;
     }
@@ -938,7 +940,7 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
         a.att = w->conv1.att, a.bias = w->conv1.bias, a.adj = L.plan.adj, a.kind = MEL_CONV_GATV2;
         a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv1.channels / (hc / 64);
         a.obs = obs, a.obs_stride = obs_width, a.node_cols = node_cols, a.aggregator = aggregator;
-        a.pooled = L.xcat, a.fid = table ? L.plan.fid : nullptr;
+        a.pooled = L.xcat, a.fid = table ? L.plan.fid : nullptr, a.legacy_walk = att_legacy_walk(w);
         StageScope t(MEL_STAGE_CONV1_ATT, s);
         if (mel_status st = launch_attend<ATT_POOL>(a, hc, s, "conv1 attention + pool")) return st;
     }

@@ -157,6 +157,13 @@ class HipForwardMixin:
     # every forward (it depends on the weights only).  Off by default: a forward then does all of its own arithmetic.
     prepared_tables = False
 
+    # A/B and tests: the attention launches walk their sources the former way (MEL_FWD_ATT_LEGACY_WALK) - same bits.
+    attention_legacy_walk = False
+
+    def _forward_flags(self, plan_ready: bool, integer_features: bool) -> int:
+        return ((_lib.FWD_PLAN_READY if plan_ready else 0) | (_lib.FWD_INTEGER_FEATURES if integer_features else 0) |
+                (_lib.FWD_ATT_LEGACY_WALK if self.attention_legacy_walk else 0))
+
     def _refresh_tables(self, w, device):
         if not self.prepared_tables or self.input_dim != 5:
             w.tables, w.tables_nodes = None, 0
@@ -290,7 +297,7 @@ class HipForwardMixin:
         if out is None:
             out = torch.empty(bs, self.output_dim, dtype=torch.float32, device=obs.device)
         stream = _lib.current_stream_ptr(obs.device)
-        w.flags = _lib.FWD_INTEGER_FEATURES if integer_features else 0
+        w.flags = self._forward_flags(False, integer_features)
         if self._MODEL in (_lib.MODEL_LDGN, _lib.MODEL_DGNR):
             fn = lib.mel_ldgn_forward if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward
             st = fn(C.byref(w), obs.data_ptr(), bs, self.agents_num, obs.shape[1], out.data_ptr(), ws.data_ptr(),
@@ -349,7 +356,7 @@ class HipForwardMixin:
         if out is None:
             out = torch.empty(bs, self.output_dim, dtype=torch.float32, device=obs_matrix.device)
         # (the struct is cached: always set, never left behind)
-        w.flags = (_lib.FWD_PLAN_READY if plan_ready else 0) | (_lib.FWD_INTEGER_FEATURES if integer_features else 0)
+        w.flags = self._forward_flags(plan_ready, integer_features)
         if select is not None:
             st = lib.mel_hldgn_forward_envs_select(C.byref(w), _lib.AGG[self.aggregator_name], obs_matrix.data_ptr(), bs,
                                                    self.agents_num, obs_matrix.stride(0), out.data_ptr(), C.byref(select),
@@ -400,7 +407,7 @@ class HipForwardMixin:
             row_offsets = torch.empty(bs + 1, dtype=torch.int32, device=obs_matrix.device)
         fn = lib.mel_ldgn_forward_agents if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward_agents
         # plan_ready: mel_env_round's plan sink wrote this call's masks; integer_features: obs rows come from the env
-        w.flags = (_lib.FWD_PLAN_READY if plan_ready else 0) | (_lib.FWD_INTEGER_FEATURES if integer_features else 0)
+        w.flags = self._forward_flags(plan_ready, integer_features)
         st = fn(C.byref(w), obs_matrix.data_ptr(), bs, self.agents_num, obs_matrix.stride(0), agent_mask.data_ptr(),
                 rows_cap, out.data_ptr(), row_offsets.data_ptr(), C.byref(select) if select is not None else None,
                 ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(obs_matrix.device))
