@@ -635,6 +635,22 @@ mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool
  * (core.py:184-187), drawn by one wavefront's MT19937. */
 mel_status mel_episode_test_seeds(uint32_t* out, int32_t n, void* stream);
 
+/* The training-graph dataset recipe (core.py:440-447) ON THE DEVICE: candidate s is nx.random_geometric_graph(n_nodes,
+ * radius, seed=s) - positions from Python's random.Random(s) (MT19937 init_by_array with the one-word key [s]; x then y per
+ * node), an edge iff dx*dx + dy*dy <= radius_sq in float64 - and is kept iff it is connected.  The call examines the seeds
+ * first_seed .. first_seed + n_candidates - 1 and appends the accepted graphs IN ASCENDING SEED ORDER at slot *count of
+ * pos [capacity, N, 2] / one_hop [capacity, N, MEL_SET_WORDS(N)] / seeds [capacity] while *count < capacity (later
+ * acceptances are dropped), then advances *count (a device counter, at most capacity afterwards).  Bit for bit the arrays of
+ * melissa_amd.env.episodes.packed_graph_pool; nothing depends on n_candidates or on scheduling, so a caller may cover a seed
+ * range in chunks of any size.  radius_sq is the caller's radius ** 2 (a double).  Three launches on `stream`, no allocation,
+ * no synchronisation; `workspace` (256-byte aligned, mel_graph_pool_workspace_bytes(n_nodes, n_candidates) bytes, 0 for
+ * arguments out of range) stages the chunk's accepted graphs.  MEL_ERR_INVALID_ARG: n_nodes outside 2 .. MEL_MAX_NODES, a
+ * null pointer, n_candidates outside [0, 2^30], or a seed range that leaves [0, 2^32). */
+size_t mel_graph_pool_workspace_bytes(int32_t n_nodes, int32_t n_candidates);
+mel_status mel_graph_pool_generate(int32_t n_nodes, double radius_sq, int64_t first_seed, int32_t n_candidates, int32_t capacity,
+                                   double* pos, uint64_t* one_hop, int64_t* seeds, int32_t* count, void* workspace,
+                                   size_t ws_bytes, void* stream);
+
 /* Scripted agents (scripted_agents_ratio > 0): the deterministic heuristics of graph_env/env/utils/heuristics/.  The
  * probabilistic ones (probabilistic_gossip / _relay) draw from the process-global np.random: not offered. */
 #define MEL_HEURISTIC_NONE                  0

@@ -43,7 +43,7 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
            "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
-           "mel_env_step_stats")
+           "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -294,6 +294,10 @@ def load(build_if_missing: bool = True):
     lib.mel_episode_test_seeds.argtypes = [vp, i32, vp]
     lib.mel_episode_refill.restype = i32
     lib.mel_episode_refill.argtypes = [C.POINTER(MelEpisodeStream), C.POINTER(MelGraphPool), P, E, i32, i32, vp]
+    lib.mel_graph_pool_workspace_bytes.restype = sz
+    lib.mel_graph_pool_workspace_bytes.argtypes = [i32, i32]
+    lib.mel_graph_pool_generate.restype = i32
+    lib.mel_graph_pool_generate.argtypes = [i32, C.c_double, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.mel_prof_create.restype = vp
     lib.mel_prof_create.argtypes = [i32]
     lib.mel_prof_destroy.restype = None

@@ -1090,6 +1090,7 @@ int32_t kprof_read_env(int32_t family, unsigned long long* out, int32_t cap) {
 }  // namespace mel
 
 #include "episode_stream.hpp"
+#include "graph_pool.hpp"
 
 using namespace mel;
 
@@ -1444,6 +1445,19 @@ mel_status mel_episode_refill(const mel_episode_stream* st, const mel_graph_pool
 
 mel_status mel_episode_test_seeds(uint32_t* out, int32_t n, void* stream) {
     return launch_episode_test_seeds(out, n, static_cast<hipStream_t>(stream));
+}
+
+// connected random geometric graphs, the dataset recipe of core.py:440-447 (graph_pool.hpp)
+size_t mel_graph_pool_workspace_bytes(int32_t n_nodes, int32_t n_candidates) {
+    if (n_nodes < 2 || n_nodes > MEL_MAX_NODES || n_candidates < 0 || n_candidates > GRAPH_POOL_MAX_CANDIDATES) return 0;
+    return carve_graph_pool(n_nodes, n_candidates, nullptr).bytes;
+}
+
+mel_status mel_graph_pool_generate(int32_t n_nodes, double radius_sq, int64_t first_seed, int32_t n_candidates, int32_t capacity,
+                                   double* pos, uint64_t* one_hop, int64_t* seeds, int32_t* count, void* workspace,
+                                   size_t ws_bytes, void* stream) {
+    return launch_graph_pool(n_nodes, radius_sq, first_seed, n_candidates, capacity, pos, one_hop, seeds, count, workspace, ws_bytes,
+                             static_cast<hipStream_t>(stream));
 }
 
 mel_status mel_wait_counter(const uint32_t* counter, uint32_t target, uint32_t timeout_us, void* stream) {

@@ -139,7 +139,10 @@ def packed_graph_pool(n: int, count: int, first_seed: int = 0, radius: float = R
     connected ones) as packed arrays - ``pos`` float64 [G, N, 2], ``one_hop`` uint64 [G, N], ``seeds`` int64 [G].  This is
     the on-disk / in-HBM dataset format that replaces the per-episode ``pickle.load`` of an ``nx.Graph``
     (core.py:165-175,450-452; the reference trains on 50 000-graph pools, README.md:92-93): see :func:`save_graph_pool`.
-    About 0.5 ms per accepted graph at N = 50 (one in four candidates is connected)."""
+    Host cost, one core: about 1.1 ms per ACCEPTED graph at N = 50 only, where one candidate in four is connected (0.26 ms per
+    candidate).  The acceptance rate falls steeply with N: at N = 20 about 3.5e-4 of the candidates are connected (7 of the
+    first 20 000 seeds), so an accepted graph there costs about 0.4 s; :func:`device_graph_pool` returns the same arrays from
+    the GPU."""
     import random
     pos_out = np.empty((count, n, 2), dtype=np.float64)
     hop_out = np.empty((count, n) + set_shape(n), dtype=np.uint64)
@@ -169,17 +172,90 @@ def load_graph_pool(path: str):
     return [Graph(pos[g], adj[g]) for g in range(pos.shape[0])]
 
 
-def cached_graph_pool(n: int, count: int, first_seed: int = 0, cache_dir: str | None = None):
-    """:func:`packed_graph_pool` through an on-disk cache (``graph_pool_n{n}_{count}_{first_seed}.npz``, default
-    directory ``$MEL_GRAPH_CACHE`` or the system temp dir): a 50 000-graph pool takes tens of seconds to draw once and
-    a fraction of a second to load afterwards."""
+SEED_LIMIT = 1 << 32                # random.Random(s) takes a one-word MT19937 key for 0 <= s < 2^32: the device generator's range
+POOL_CHUNK_BYTES = 64 << 20         # device_graph_pool: workspace budget of one launch
+
+
+def default_pool_chunk(n: int) -> int:
+    """Candidates per launch of :func:`device_graph_pool`: as many as stage their graphs (16 N bytes of positions, 8 N W
+    of node sets, a 4-byte slot) in ``POOL_CHUNK_BYTES`` = 64 MiB of workspace - 139 810 at N = 20, 55 831 at N = 50,
+    16 368 at N = 128."""
+    return POOL_CHUNK_BYTES // (int(n) * (16 + 8 * set_words(n)) + 4)
+
+
+def device_graph_pool(n: int, count: int, first_seed: int = 0, radius: float = RADIUS_OF_INFLUENCE, device="cuda",
+                      chunk: int | None = None):
+    """:func:`packed_graph_pool` on the GPU: the same ``pos`` float64 [G, N, 2], ``one_hop`` uint64 [G, N] ([G, N, 2] beyond
+    64 nodes) and ``seeds`` int64 [G], bit for bit (``mel_graph_pool_generate``, csrc/graph_pool.hpp: one wavefront per
+    candidate seed, accepted graphs written in ascending seed order).  Candidates are examined ``chunk`` per launch until
+    ``count`` graphs are accepted; what the last chunk accepts beyond ``count`` is dropped, so the result does not depend on
+    ``chunk``.  Default chunk: :func:`default_pool_chunk` - what fits a fixed 64 MiB workspace at this N.  ValueError for more
+    than 128 nodes, and when the seeds below 2^32 (the range in which ``random.Random(s)`` takes a one-word key) run out before
+    ``count`` graphs are found."""
+    from .. import _lib
+    _lib.check_n_nodes(n, "device_graph_pool")
+    n, count, first_seed = int(n), int(count), int(first_seed)
+    if n < 2 or count < 0 or not (0 <= first_seed < SEED_LIMIT):
+        raise ValueError(f"device_graph_pool: n={n} (>= 2), count={count} (>= 0), first_seed={first_seed} (in [0, 2^32))")
+    chunk = default_pool_chunk(n) if chunk is None else int(chunk)
+    if not (1 <= chunk <= 1 << 30):
+        raise ValueError(f"device_graph_pool: chunk={chunk} must be in [1, 2^30]")
+    import torch
+    lib = _lib.load()
+    dev = torch.device(device)
+    w = set_words(n)
+    with torch.cuda.device(dev):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        pos = torch.empty((max(count, 1), n, 2), dtype=torch.float64, device=dev)
+        hop = torch.empty((max(count, 1), n, w), dtype=torch.int64, device=dev)
+        seeds = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+        counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws_bytes = int(lib.mel_graph_pool_workspace_bytes(n, chunk))
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        got, s = 0, first_seed
+        while got < count:
+            if s >= SEED_LIMIT:
+                raise ValueError(f"device_graph_pool: only {got} of {count} connected {n}-node graphs among the seeds "
+                                 f"{first_seed} .. 2^32 - 1")
+            m = min(chunk, SEED_LIMIT - s)
+            _lib.check(lib.mel_graph_pool_generate(n, float(radius) ** 2, s, m, count, pos.data_ptr(), hop.data_ptr(),
+                                                   seeds.data_ptr(), counter.data_ptr(), workspace.data_ptr(), ws_bytes,
+                                                   _lib.current_stream_ptr(dev)), "mel_graph_pool_generate")
+            s += m
+            got = int(counter.item())
+        pos_out = pos[:count].cpu().numpy()
+        hop_out = hop[:count].cpu().numpy().view(np.uint64).reshape((count, n) + set_shape(n))
+        return pos_out, hop_out, seeds[:count].cpu().numpy()
+
+
+def generate_graph_pool(n: int, count: int, first_seed: int = 0, radius: float = RADIUS_OF_INFLUENCE, device=None):
+    """The packed arrays of :func:`packed_graph_pool`, from :func:`device_graph_pool` when this process has a GPU (``device``
+    or the current one; a library that does not load is an error there, not a reason to fall back) and from the host loop
+    when it has none.  The arrays are the same either way."""
+    import torch
+    if torch.cuda.is_available():
+        return device_graph_pool(n, count, first_seed, radius, device="cuda" if device is None else device)
+    return packed_graph_pool(n, count, first_seed, radius)
+
+
+def connected_graph_pool(n: int, count: int, first_seed: int = 0, device=None):
+    """The graphs of :func:`synthetic_graph_pool` as a list of :class:`Graph` views over :func:`generate_graph_pool`'s
+    arrays: what ``train`` and ``watch`` build their pools with."""
+    pos, hop, _ = generate_graph_pool(n, count, first_seed, device=device)
+    return [Graph(pos[g], hop[g]) for g in range(count)]
+
+
+def cached_graph_pool(n: int, count: int, first_seed: int = 0, cache_dir: str | None = None, device=None):
+    """:func:`generate_graph_pool` (the device generator with a GPU, :func:`packed_graph_pool` without: the same arrays)
+    through an on-disk cache (``graph_pool_n{n}_{count}_{first_seed}.npz``, default directory ``$MEL_GRAPH_CACHE`` or the
+    system temp dir): a fraction of a second to load afterwards."""
     import os
     import tempfile
     cache_dir = cache_dir or os.environ.get("MEL_GRAPH_CACHE") or os.path.join(tempfile.gettempdir(), "melissa_graph_pools")
     os.makedirs(cache_dir, exist_ok=True)
     path = os.path.join(cache_dir, f"graph_pool_n{n}_{count}_{first_seed}.npz")
     if not os.path.exists(path):
-        pos, hop, seeds = packed_graph_pool(n, count, first_seed)
+        pos, hop, seeds = generate_graph_pool(n, count, first_seed, device=device)
         tmp = f"{path}.tmp.{os.getpid()}.npz"
         save_graph_pool(tmp, pos, hop, seeds)
         os.replace(tmp, path)
@@ -309,3 +385,28 @@ def pack_episodes(episodes, graphs, n: int, max_moves: int, dynamic: bool):
         if dynamic:
             moves[k] = movement_offsets(ep.movement_seed, n, max_moves)
     return dict(pos=pos, one_hop=one_hop, interested=interested, origin=origin, moves=moves, scripted=scripted)
+
+
+def arg_parser():
+    import argparse
+    ap = argparse.ArgumentParser(description="write a packed pool of connected random geometric graphs (the file --graph-pool of "
+                                             "melissa_amd.train / melissa_amd.watch reads)")
+    ap.add_argument("--nodes", type=int, required=True)
+    ap.add_argument("--graphs", type=int, required=True)
+    ap.add_argument("--first-seed", type=int, default=0)
+    ap.add_argument("--out", required=True, metavar="FILE")
+    return ap
+
+
+def main(argv=None):
+    """``python -m melissa_amd.env.episodes --nodes N --graphs G [--first-seed S] --out FILE``: the pool of
+    :func:`generate_graph_pool` (drawn on the GPU when there is one) in :func:`save_graph_pool`'s format."""
+    a = arg_parser().parse_args(argv)
+    pos, hop, seeds = generate_graph_pool(a.nodes, a.graphs, a.first_seed)
+    save_graph_pool(a.out, pos, hop, seeds)
+    print(f"{a.out}: {a.graphs} connected {a.nodes}-node graphs, seeds {int(seeds[0]) if a.graphs else '-'} .. "
+          f"{int(seeds[-1]) if a.graphs else '-'}")
+
+
+if __name__ == "__main__":
+    main()

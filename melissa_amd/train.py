@@ -74,8 +74,8 @@ def _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scri
     import numpy as np
     from . import _lib
     from .collect import Collector
-    from .env import HipGraphVectorEnv, synthetic_graph_pool
-    venv = HipGraphVectorEnv(1, n_nodes, graph_pool=synthetic_graph_pool(n_nodes, 16, first_seed=0), dynamic_graph=True,
+    from .env import HipGraphVectorEnv, connected_graph_pool
+    venv = HipGraphVectorEnv(1, n_nodes, graph_pool=connected_graph_pool(n_nodes, 16, first_seed=0, device=device), dynamic_graph=True,
                              device=device, max_moves=64, seed=seed, construct_like_reference=False, is_testing=True,
                              num_test_episodes=test_num, scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic)
     col = Collector(policy, venv, episodes_per_env=test_num + 2, seed=seed, eps=eps_test, chunk=4, use_graph=False)
@@ -100,8 +100,8 @@ def _evaluate_spread(policy, n_nodes, test_num, test_envs, eps_test, seed, devic
     import numpy as np
     from . import _lib
     from .collect import evaluate_spread
-    from .env import HipGraphVectorEnv, synthetic_graph_pool
-    venv = HipGraphVectorEnv(test_envs, n_nodes, graph_pool=synthetic_graph_pool(n_nodes, 16, first_seed=0), dynamic_graph=True,
+    from .env import HipGraphVectorEnv, connected_graph_pool
+    venv = HipGraphVectorEnv(test_envs, n_nodes, graph_pool=connected_graph_pool(n_nodes, 16, first_seed=0, device=device), dynamic_graph=True,
                              device=device, max_moves=64, seed=seed, construct_like_reference=False, is_testing=True,
                              num_test_episodes=test_num, scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic,
                              spread_test_episodes=True)
@@ -287,11 +287,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
           heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
-          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes"):
+          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes", graph_pool=None):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
-    pools >= 4096 go through the on-disk packed cache, ``melissa_amd.env.cached_graph_pool``).  Episodes come from the
+    pools >= 4096 go through the on-disk packed cache, ``melissa_amd.env.cached_graph_pool``); the graphs are drawn by the
+    device generator (``melissa_amd.env.device_graph_pool``), the same ones the host loop ``synthetic_graph_pool`` finds.
+    ``graph_pool``: a packed ``.npz`` file (``save_graph_pool``, ``python -m melissa_amd.env.episodes``) that is the training
+    pool instead; ``graphs`` is then not used.  Episodes come from the
     device episode stream: every reset draws a new (graph, source, interested set, movement seed) like World.reset.
     ``capture_updates``: replay the update from HIP graphs (``DQNLearner.capture``; DGN-R and N-DGN too: their dense sibling forms
     have static shapes, replay.DGNLearner / replay.NDGNLearner).  None = on unless a probe is attached; with several ranks the collective stays
@@ -339,7 +342,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     import torch
     from . import launch, parallel
     from .collect import EpsSchedule, RoundLoop
-    from .env import HipGraphVectorEnv, synthetic_graph_pool
+    from .env import HipGraphVectorEnv, cached_graph_pool, connected_graph_pool, load_graph_pool
     from .replay import PrioritizedRoundReplay, RoundReplay
     if backend != "gloo":
         launch.check_rank_device()                             # exit 2 when LOCAL_RANK names a GPU this rank cannot see
@@ -357,8 +360,15 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         policy.load_state_dict(torch.load(resume_path, map_location=device, weights_only=True))
         parallel.broadcast_parameters(net, src=0)
     checksum_start = _param_checksum(net) if epoch is not None else None      # (what the first update starts from)
-    from .env import cached_graph_pool
-    graph_list = cached_graph_pool(n_nodes, graphs, 0) if graphs >= 4096 else synthetic_graph_pool(n_nodes, graphs, first_seed=0)
+    if graph_pool is not None:
+        graph_list = load_graph_pool(graph_pool)
+        if len(graph_list) < 1 or graph_list[0].pos.shape[0] != n_nodes:
+            raise ValueError(f"graph_pool={graph_pool!r} holds {len(graph_list)} graphs of "
+                             f"{graph_list[0].pos.shape[0] if graph_list else 0} nodes, not of {n_nodes}")
+    elif graphs >= 4096:
+        graph_list = cached_graph_pool(n_nodes, graphs, 0, device=device)
+    else:
+        graph_list = connected_graph_pool(n_nodes, graphs, first_seed=0, device=device)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False, heuristic=heuristic,
                              scripted_agents_ratio=scripted_agents_ratio)
@@ -490,6 +500,8 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--backend", default=None)
     ap.add_argument("--graphs", type=int, default=16, help="training-graph dataset size (50000 = the reference's)")
+    ap.add_argument("--graph-pool", default=None, metavar="FILE",
+                    help="packed training-graph dataset (.npz of python -m melissa_amd.env.episodes) used instead of --graphs")
     ap.add_argument("--gpus", type=int, default=1, help="ranks to start (one per GPU) when not under torch.distributed.run")
     ap.add_argument("--capture-updates", choices=["auto", "on", "off"], default="auto",
                     help="replay the DQN update from HIP graphs (auto: on; the capture runs 2 extra untimed warm-up updates first, "
@@ -548,7 +560,7 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
                 seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq,
                 update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size,
-                test_envs=a.test_envs, collect_stats=a.collect_stats)
+                test_envs=a.test_envs, collect_stats=a.collect_stats, graph_pool=a.graph_pool)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -557,6 +569,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     a = ap.parse_args(argv)
     if a.update_per_step is not None and a.epoch is None:
         ap.error("--update-per-step paces the updates of the epoch mode: it needs --epoch")
+    import sys
+    given = sys.argv[1:] if argv is None else argv
+    if a.graph_pool is not None and any(x == "--graphs" or x.startswith("--graphs=") for x in given):
+        print(f"--graph-pool {a.graph_pool} is the training pool: --graphs {a.graphs} is ignored", file=sys.stderr)
     return a
 
 

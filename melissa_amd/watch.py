@@ -24,14 +24,17 @@ import json
 import torch
 
 from .collect import Collector, evaluate_spread
-from .env import HipGraphVectorEnv, synthetic_graph_pool
+from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
 from .train import N_DGN_NETWORK, build_network
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
-          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes"):
-    """``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
+          dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
+          graphs=16):
+    """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
+    random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
+    ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
     statistic, pooled on the device; ``n_info_rows`` steps) instead of over the episodes' final rows.  Not with ``spread``:
     the envs that finish their share early keep playing, and those surplus episodes would enter the pool."""
     if spread and collect_stats != "episodes":
@@ -43,7 +46,9 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         policy.load_state_dict(torch.load(load, map_location=device, weights_only=True))
     net.eval()
     net.set_feature_dtype(feature_dtype)
-    pool = graph_pool if graph_pool is not None else synthetic_graph_pool(n_nodes, 16, first_seed=0)
+    if isinstance(graph_pool, str):
+        graph_pool = load_graph_pool(graph_pool)
+    pool = graph_pool if graph_pool is not None else connected_graph_pool(n_nodes, graphs, first_seed=0, device=device)
     if spread:
         envs = min(envs, episodes)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=pool, dynamic_graph=dynamic_graph, device=device, max_moves=64,
@@ -70,6 +75,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--envs", type=int, default=1)
     ap.add_argument("--episodes", type=int, default=10)
     ap.add_argument("--load", default=None)
+    ap.add_argument("--graphs", type=int, default=16, help="evaluation-graph pool size")
+    ap.add_argument("--graph-pool", default=None, metavar="FILE",
+                    help="packed graph dataset (.npz of python -m melissa_amd.env.episodes) used instead of --graphs")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f32s", "f32a"])
     ap.add_argument("--heuristic", default=None, choices=["simple_broadcast", "broadcast_if_any_interested", "silent", "mpr"],
                     help="heuristic the scripted agents run (common.py:67)")
@@ -89,8 +97,13 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.spread and a.collect_stats != "episodes":
         ap.error("--collect-stats steps is not offered with --spread (surplus episodes would enter the pool)")
+    import sys
+    given = sys.argv[1:] if argv is None else argv
+    if a.graph_pool is not None and any(x == "--graphs" or x.startswith("--graphs=") for x in given):
+        print(f"--graph-pool {a.graph_pool} is the graph pool: --graphs {a.graphs} is ignored", file=sys.stderr)
     print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype, heuristic=a.heuristic,
-                           scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread, collect_stats=a.collect_stats)))
+                           scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread, collect_stats=a.collect_stats,
+                           graph_pool=a.graph_pool, graphs=a.graphs)))
 
 
 if __name__ == "__main__":
