@@ -109,7 +109,7 @@ typedef struct mel_weights {
     mel_mlp   v_head;      /* latent -> ... -> 1                                     */
     int32_t precision;     /* MEL_PREC_F32 (reference arithmetic, logits <= 1e-4), MEL_PREC_BF16, MEL_PREC_F32_SPLIT or MEL_PREC_F32_AUTO */
     int32_t flags;         /* MEL_FWD_PLAN_READY: the plan masks of this call were written by mel_env_round (plan_* sink);
-                            * MEL_FWD_INTEGER_FEATURES, MEL_FWD_ATT_LEGACY_WALK: see below */
+                            * MEL_FWD_INTEGER_FEATURES: see below.  The value 4 is reserved (it once chose a former attention walk) */
     const void* prepared;  /* optional (MEL_PREC_BF16 / MEL_PREC_F32_SPLIT): device buffer filled by mel_prepare_weights for THESE
                             * weights - the forward then reads the converted projection weights from it and launches no
                             * conversion.  NULL: every call converts the fp32 parameters into its workspace (stateless). */
@@ -130,10 +130,6 @@ typedef struct mel_weights {
  * id.  Same arithmetic per row, bit-identical logits.  A feature outside the ranges is clamped into the table and flagged
  * (mel_forward_tap kind 3).  Without the flag the general row-list path runs (arbitrary float features). */
 #define MEL_FWD_INTEGER_FEATURES 2
-/* MEL_FWD_ATT_LEGACY_WALK: the attention launches of this call pick their sources off the node set in every online-softmax step
- * (the walk before the per-target source list, csrc/attention.hpp) - same bits, kept for one release so that tests and A/B runs
- * compare the two in one process.  The environment variable MEL_ATT_LEGACY_WALK (read once per process) sets it for every call. */
-#define MEL_FWD_ATT_LEGACY_WALK 4
 
 /* Feature precision of the L-DGN / DGN-R forward (BASELINE config "bf16 feature path").  MEL_PREC_BF16: the
  * node-feature rows between layers (encoder output, lin_l / lin_r projections, conv outputs, head input and

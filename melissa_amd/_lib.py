@@ -47,7 +47,6 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
-FWD_ATT_LEGACY_WALK = 4     # mel_weights.flags: the attention launches walk their sources the former way (same bits; A/B and tests)
 HEURISTICS = {None: 0, "simple_broadcast": 1, "broadcast_if_any_interested": 2, "silent": 3, "mpr": 4}
 LOGGER_KEYS = ("total_messages_transmitted", "coverage", "messages_sent", "messages_received", "n_neighbours",
                "interested_agents", "coverage_interested_fraction", "coverage_interested_count",

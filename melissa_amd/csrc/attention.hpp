@@ -49,7 +49,6 @@ struct AttArgs {
     // node-feature table mode (plan_masks.hpp): xl / xr / h0 are TABLES indexed by a node's tuple id fid[b*N + i] instead of
     // row lists indexed by packed position (null = row lists)
     const int32_t* fid;
-    int legacy_walk;            // MEL_FWD_ATT_LEGACY_WALK / MEL_ATT_LEGACY_WALK: the per-step source selection (ATT_WALK_LEGACY)
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -165,15 +164,14 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 // table row of the source's tuple (one v_readlane) instead of its packed position in the row list.
 //
 // How a target's sources are walked (ATT_WALK_*).  The arithmetic of a step (attend_step) and the source order - ascending
-// node id, G per step - are the same in every form, so the output bits are too.
-//   LEGACY   every step picks its G sources off the 64-bit set (ffbl chains, readfirstlane) and decides table mode and the
-//            lanes per head at run time: the walk before the list forms, kept selectable for one release
-//            (MEL_FWD_ATT_LEGACY_WALK / MEL_ATT_LEGACY_WALK)
-//   the list forms build the target's source list ONCE - lane k holds the row index of the k-th source - and a step takes its G
+// node id, G per step - are the same in every form, so the output bits are too (tests/test_gpu_attention_walk.py holds them
+// to the bits of the walk these forms replaced, which picked its G sources off the node set in every step).
+//   Every form builds the target's source list ONCE - lane k holds the row index of the k-th source - and a step takes its G
 //   row indices from that register with v_readlane: no set arithmetic and no launch-uniform branch inside a step
 //   GENERIC  table mode and the lanes per head decided at run time (any shape)
 //   LIST_16 / TABLE_16  row-list / table mode with 16 lanes per head, both known at compile time (the headline shapes)
-enum { ATT_WALK_LEGACY = 0, ATT_WALK_GENERIC = 1, ATT_WALK_LIST_16 = 2, ATT_WALK_TABLE_16 = 3 };
+// (the values are part of the kernels' mangled names, which profiles and kernel traces quote: 0 was the former walk)
+enum { ATT_WALK_GENERIC = 1, ATT_WALK_LIST_16 = 2, ATT_WALK_TABLE_16 = 3 };
 
 template <int FORM>
 __device__ __forceinline__ bool att_table_mode(const AttArgs& a) {
@@ -267,71 +265,48 @@ __device__ __forceinline__ Vec<VPL> attend_target(const AttArgs& a, size_t xr_ro
     Vec<VPL> acc;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) acc.v[i] = 0.f;
-    if constexpr (FORM == ATT_WALK_LEGACY) {
-        const bool table = a.fid != nullptr;
-        while (ns_any(sources)) {                    // TransformerConv adds no self-loop: a target may be isolated
-            size_t row[G];                           // element index of this lane's slice of the source row
+    constexpr int LPH = FORM == ATT_WALK_GENERIC ? 0 : 16;
+    constexpr int CHUNK = 64 - 64 % G;           // sources per list: whole steps, one lane each (the neighbour cap keeps a
+                                                 // target at 34 sources, so this loop runs once; it is here for the bound)
+    NodeSet<W> left = ns_uniform(sources);       // SGPRs: the list is built by scalar instructions
+    int count = ns_count(left);
+    while (count > 0) {                          // TransformerConv adds no self-loop: a target may be isolated
+        const int nl = min(count, CHUNK);
+        // lane k: node id of the k-th source in ascending order; the lanes past the list keep node 0, whose row is
+        // the valid row an off slot re-reads
+        int node = 0;
+        for (int k = 0; k < nl; ++k) {
+            node = lane == k ? ns_lowest(left) : node;       // scalar walk of the set, one compare + select per source
+            ns_clear_lowest(left);
+        }
+        int rowv;                                // ... and the row index of that node: its tuple id, or its packed position
+        if (att_table_mode<FORM>(a)) {
+            if constexpr (W == 1) rowv = __builtin_amdgcn_ds_bpermute(node << 2, my_fid[0]);
+            else {
+                const int lo = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[0]);
+                const int hi = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[1]);
+                rowv = node < 64 ? lo : hi;
+            }
+        } else {
+            rowv = soff + ns_rank_below(smask, node);
+        }
+        for (int s0 = 0; s0 < nl; s0 += G) {
+            Vec<VPL> xl[G], xv[G];
             bool on[G];
 #pragma unroll
             for (int k = 0; k < G; ++k) {
-                on[k] = ns_any(sources);
-                const int j = on[k] ? ns_lowest(sources) : 0;
-                ns_clear_lowest(sources);            // empty stays empty
-                const int srow = table ? node_i32<W>(my_fid, j) : soff + (on[k] ? ns_rank_below(smask, j) : 0);
-                row[k] = (size_t)srow * a.ld_l + lane * VPL;                     // off slots re-read a valid row
+                on[k] = s0 + k < nl;             // slot 0 is always on
+                const float* src = source_row<BF>(a.xl, __builtin_amdgcn_readlane(rowv, s0 + k), a.ld_l);
+                xl[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL));
+                if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL + HC));
             }
-            Vec<VPL> xl[G], xv[G];
-#pragma unroll
-            for (int k = 0; k < G; ++k) {
-                xl[k] = load_row<VPL, BF>(a.xl, row[k]);
-                if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(a.xl, row[k] + HC);
-            }
-            attend_step<VPL, KIND, G, 0>(a, xr, att, xl, xv, on, m, l, acc);
+            // every row load of the step is in flight before its arithmetic starts (left alone, the scheduler sinks the
+            // second source's loads below the first source's score: one memory latency after the other).  Not for bf16 rows:
+            // their loads are issued together anyway, and holding both rows unpacked costs 16 VGPRs and a wave per SIMD
+            if constexpr (!BF) __builtin_amdgcn_sched_barrier(0);
+            attend_step<VPL, KIND, G, LPH>(a, xr, att, xl, xv, on, m, l, acc);
         }
-    } else {
-        constexpr int LPH = FORM == ATT_WALK_GENERIC ? 0 : 16;
-        constexpr int CHUNK = 64 - 64 % G;           // sources per list: whole steps, one lane each (the neighbour cap keeps a
-                                                     // target at 34 sources, so this loop runs once; it is here for the bound)
-        NodeSet<W> left = ns_uniform(sources);       // SGPRs: the list is built by scalar instructions
-        int count = ns_count(left);
-        while (count > 0) {                          // TransformerConv adds no self-loop: a target may be isolated
-            const int nl = min(count, CHUNK);
-            // lane k: node id of the k-th source in ascending order; the lanes past the list keep node 0, whose row is
-            // the valid row an off slot re-reads
-            int node = 0;
-            for (int k = 0; k < nl; ++k) {
-                node = lane == k ? ns_lowest(left) : node;       // scalar walk of the set, one compare + select per source
-                ns_clear_lowest(left);
-            }
-            int rowv;                                // ... and the row index of that node: its tuple id, or its packed position
-            if (att_table_mode<FORM>(a)) {
-                if constexpr (W == 1) rowv = __builtin_amdgcn_ds_bpermute(node << 2, my_fid[0]);
-                else {
-                    const int lo = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[0]);
-                    const int hi = __builtin_amdgcn_ds_bpermute((node & 63) << 2, my_fid[1]);
-                    rowv = node < 64 ? lo : hi;
-                }
-            } else {
-                rowv = soff + ns_rank_below(smask, node);
-            }
-            for (int s0 = 0; s0 < nl; s0 += G) {
-                Vec<VPL> xl[G], xv[G];
-                bool on[G];
-#pragma unroll
-                for (int k = 0; k < G; ++k) {
-                    on[k] = s0 + k < nl;             // slot 0 is always on
-                    const float* src = source_row<BF>(a.xl, __builtin_amdgcn_readlane(rowv, s0 + k), a.ld_l);
-                    xl[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL));
-                    if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL + HC));
-                }
-                // every row load of the step is in flight before its arithmetic starts (left alone, the scheduler sinks the
-                // second source's loads below the first source's score: one memory latency after the other).  Not for bf16 rows:
-                // their loads are issued together anyway, and holding both rows unpacked costs 16 VGPRs and a wave per SIMD
-                if constexpr (!BF) __builtin_amdgcn_sched_barrier(0);
-                attend_step<VPL, KIND, G, LPH>(a, xr, att, xl, xv, on, m, l, acc);
-            }
-            count -= nl;
-        }
+        count -= nl;
     }
     const float inv = __builtin_amdgcn_rcpf(l + 1e-16f);
     Vec<VPL> out;
@@ -430,8 +405,8 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
     const int vblock = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     const int rows_pad = ((rows + 4 * (int)gridDim.x - 1) / (4 * (int)gridDim.x)) * (4 * (int)gridDim.x);
     const int span = rows_pad >> 3;              // rows each XCD owns (multiple of 4 * per_xcd)
-    // the list forms keep the wave's number, and with it the row index and everything addressed by it, in SGPRs
-    const int wave = FORM == ATT_WALK_LEGACY ? (int)(threadIdx.x >> 6) : uniform_i32(threadIdx.x >> 6);
+    // the wave's number, and with it the row index and everything addressed by it, in SGPRs
+    const int wave = uniform_i32(threadIdx.x >> 6);
     for (int i = (vblock % per_xcd) * 4 + wave; i < span; i += per_xcd * 4) {
         const int r = (blockIdx.x & 7) * span + i;
         if (r >= rows) continue;
@@ -539,48 +514,37 @@ __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
 // size 128 with four heads, which every configuration BASELINE quotes runs at; every other shape takes the generic list walk.
 template <int V, int MODE>
 static int att_walk_form(const AttArgs& a) {
-    if (a.legacy_walk) return ATT_WALK_LEGACY;
     if (V == 8 && a.lanes_per_head == 16) return (MODE != ATT_SINGLE && a.fid) ? ATT_WALK_TABLE_16 : ATT_WALK_LIST_16;
     return ATT_WALK_GENERIC;
 }
 
 template <int V, int MODE, int FORM>
 static void launch_attend_form(const AttArgs& a, int grid, hipStream_t s) {
-    if constexpr (MODE == ATT_POOL) {
-        if (a.n > 64) {             // graphs of 65 .. 128 nodes: two-word node sets
-            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 16, 2, FORM>), dim3(a.bs), dim3(1024), 0, s, a);
-            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 16, 2, FORM>), dim3(a.bs), dim3(1024), 0, s, a);
-        } else if (a.bs >= 2048) {
-            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, 4, 1, FORM>), dim3(a.bs), dim3(256), 0, s, a);
-            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, 4, 1, FORM>), dim3(a.bs), dim3(256), 0, s, a);
+    with_flag(a.bf16, [&](auto bf) {
+        constexpr bool BF = decltype(bf)::value;
+        if constexpr (MODE == ATT_POOL) {
+            auto launch = [&](auto nw, auto w) {        // NW waves per env, node sets of W words
+                constexpr int NW = decltype(nw)::value;
+                MEL_LAUNCH((gat_attend_pool_kernel<V, BF, NW, decltype(w)::value, FORM>), dim3(a.bs), dim3(64 * NW), 0, s, a);
+            };
+            if (a.n > 64) launch(int_c<16>{}, int_c<2>{});              // graphs of 65 .. 128 nodes: two-word node sets
+            else if (a.bs >= 2048) launch(int_c<4>{}, int_c<1>{});
+            else launch(int_c<MEL_POOL_NW>{}, int_c<1>{});
         } else {
-            if (a.bf16) MEL_LAUNCH((gat_attend_pool_kernel<V, true, MEL_POOL_NW, 1, FORM>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);
-            else MEL_LAUNCH((gat_attend_pool_kernel<V, false, MEL_POOL_NW, 1, FORM>), dim3(a.bs), dim3(64 * MEL_POOL_NW), 0, s, a);
+            with_words(a.n, [&](auto w) {
+                with_flag(a.kind == MEL_CONV_TRANSFORMER, [&](auto tconv) {
+                    constexpr int KIND = decltype(tconv)::value ? MEL_CONV_TRANSFORMER : MEL_CONV_GATV2;
+                    MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, KIND, BF, decltype(w)::value, FORM>), dim3(grid), dim3(256), 0, s, a);
+                });
+            });
         }
-    } else {
-#define MEL_ATT_LAUNCH_W(WW)                                                                                                   \
-    if (a.kind == MEL_CONV_TRANSFORMER && a.bf16)                                                                              \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, true, WW, FORM>), dim3(grid), dim3(256), 0, s, a);   \
-    else if (a.kind == MEL_CONV_TRANSFORMER)                                                                                   \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_TRANSFORMER, false, WW, FORM>), dim3(grid), dim3(256), 0, s, a);  \
-    else if (a.bf16)                                                                                                           \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, true, WW, FORM>), dim3(grid), dim3(256), 0, s, a);         \
-    else                                                                                                                       \
-        MEL_LAUNCH((gat_attend_rows_kernel<V, MODE, MEL_CONV_GATV2, false, WW, FORM>), dim3(grid), dim3(256), 0, s, a);
-        if (a.n > 64) {
-            MEL_ATT_LAUNCH_W(2)
-        } else {
-            MEL_ATT_LAUNCH_W(1)
-        }
-#undef MEL_ATT_LAUNCH_W
-    }
+    });
 }
 
 // V channels per lane: the launch in the walk form of its arguments - only the forms att_walk_form can name are instantiated
 template <int V, int MODE>
 static void launch_attend_v(const AttArgs& a, int grid, hipStream_t s) {
     switch (att_walk_form<V, MODE>(a)) {
-        case ATT_WALK_LEGACY: launch_attend_form<V, MODE, ATT_WALK_LEGACY>(a, grid, s); break;
         case ATT_WALK_LIST_16:
             if constexpr (V == 8) launch_attend_form<V, MODE, ATT_WALK_LIST_16>(a, grid, s);
             break;

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/melissa_hip.h"
 
 namespace mel {
@@ -77,6 +79,21 @@ inline bool launch_events(hipEvent_t* begin, hipEvent_t* end) {
         else                                                                                                 \
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                             \
     } while (0)
+
+// Host-side dispatch of a template argument by a run-time value: f is a generic lambda and gets the choice as a compile-time
+// constant (decltype(c)::value), so a launch that exists once per node-set width or per feature type is WRITTEN once.
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <typename F>
+inline void with_words(int n_nodes, F&& f) {      // node sets of one 64-bit word, two for graphs of 65 .. 128 nodes
+    if (n_nodes > 64) f(int_c<2>{});
+    else f(int_c<1>{});
+}
+template <typename F>
+inline void with_flag(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -1189,13 +1189,11 @@ mel_status mel_env_round(mel_env_batch* env, const mel_episode_pool* pool, const
     StageScope t(MEL_STAGE_ENV_STEP, static_cast<hipStream_t>(stream));
     const dim3 grid((env->n_envs + 3) / 4);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (env->step_stats) {
-        if (env->n_nodes > 64) MEL_LAUNCH((env_round_kernel<2, true>), grid, dim3(256), 0, s, a);
-        else MEL_LAUNCH((env_round_kernel<1, true>), grid, dim3(256), 0, s, a);
-    } else {
-        if (env->n_nodes > 64) MEL_LAUNCH((env_round_kernel<2, false>), grid, dim3(256), 0, s, a);
-        else MEL_LAUNCH((env_round_kernel<1, false>), grid, dim3(256), 0, s, a);
-    }
+    with_words(env->n_nodes, [&](auto w) {
+        with_flag(env->step_stats != nullptr, [&](auto stats) {
+            MEL_LAUNCH((env_round_kernel<decltype(w)::value, decltype(stats)::value>), grid, dim3(256), 0, s, a);
+        });
+    });
     return check_launch("env_round");
 }
 

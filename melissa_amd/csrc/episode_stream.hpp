@@ -424,8 +424,7 @@ static mel_status launch_episode_refill(const mel_episode_stream* st, const mel_
 #else
     const int grid = (int)(expect < 256 ? 256 : (expect > 4096 ? 4096 : expect));
 #endif
-    if (env->n_nodes > 64) MEL_LAUNCH(episode_fill_kernel<2>, dim3(grid), dim3(64), 0, stream, a);
-    else MEL_LAUNCH(episode_fill_kernel<1>, dim3(grid), dim3(64), 0, stream, a);
+    with_words(env->n_nodes, [&](auto w) { MEL_LAUNCH(episode_fill_kernel<decltype(w)::value>, dim3(grid), dim3(64), 0, stream, a); });
     MEL_LAUNCH(episode_publish_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a);
     return check_launch("episode_refill");
 }

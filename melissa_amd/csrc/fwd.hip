@@ -476,8 +476,6 @@ static FeatureTables carve_tables(const mel_weights* w, int n, void* buf, size_t
     if (bytes) *bytes = c.off;
     return t;
 }
-// the attention launches of this call in the former source walk: the caller's flag, or MEL_ATT_LEGACY_WALK for the process
-static int att_legacy_walk(const mel_weights* w) { return (w->flags & MEL_FWD_ATT_LEGACY_WALK) || gemm_tuning().att_legacy_walk; }
 // The shapes table_fused_tile is built for (gemm_table.hpp): GATv2 L-DGN on the exact-fp32 instruction - MEL_PREC_F32, and
 // MEL_PREC_F32_AUTO, whose table launches are far too small for the split kernels.  Everything else (the bf16 feature path,
 // MEL_PREC_F32_SPLIT, DGN-R's three source-side matrices, HL-DGN) keeps the two-launch form.
@@ -637,10 +635,8 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
             const int tiles = enc.grid;
             if (n > 64) MEL_LAUNCH(plan_enc_kernel<2>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
             else MEL_LAUNCH(plan_enc_kernel<1>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
-        } else if (n > 64) {
-            MEL_LAUNCH(plan_lists_kernel<2>, dim3((bs + 3) / 4), dim3(256), 0, s, pa);
         } else {
-            MEL_LAUNCH(plan_lists_kernel<1>, dim3((bs + 3) / 4), dim3(256), 0, s, pa);
+            with_words(n, [&](auto w) { MEL_LAUNCH(plan_lists_kernel<decltype(w)::value>, dim3((bs + 3) / 4), dim3(256), 0, s, pa); });
         }
         if (mel_status st = check_launch("plan_lists")) return st;
     }
@@ -687,7 +683,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.out = L.h1, a.ldo = hc, a.xcat = L.xcat, a.ld_cat = latent, a.hidden = hidden, a.h0 = ft.h0;
         if (conv2.kernel == GemmKernel::PLANES) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
         a.out_scale = L.plan.dm1;       // the decision-maker mask (l_dgn.py:128) is applied as h1 is stored; x_2 is taken before it
-        a.fid = table ? L.plan.fid : nullptr, a.legacy_walk = att_legacy_walk(w);
+        a.fid = table ? L.plan.fid : nullptr;
         StageScope t(MEL_STAGE_CONV1_ATT, s);
         if (mel_status st = launch_attend<ATT_ROWS>(a, hc, s, "conv1 attention")) return st;
     }
@@ -702,7 +698,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.adj = L.plan.adj;
         a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv2.channels / (hc / 64);
         a.desc = L.plan.desc2, a.rows_dev = nL, a.rows_cap = R, a.rows_hint = hintL;
-        a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc, a.legacy_walk = att_legacy_walk(w);
+        a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc;
         StageScope t(MEL_STAGE_CONV2_ATT, s);
         if (mel_status st = launch_attend<ATT_SINGLE>(a, hc, s, "conv2 attention")) return st;
     }
@@ -881,10 +877,10 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
         StageScope t(MEL_STAGE_PLAN, s);
         // hl_dgn.py:108 pools over the whole graph: the controlling index is read (and clamped) but unused
         if (!((w->flags & MEL_FWD_PLAN_READY) && !index_col)) {      // (else: written by mel_env_round's plan sink)
-            if (n > 64) MEL_LAUNCH(plan_masks_kernel<2>, dim3((bs + 3) / 4), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols,
-                                   (const uint64_t*)nullptr, L.plan, index_col ? 0 : -1);
-            else MEL_LAUNCH(plan_masks_kernel<1>, dim3((bs + 3) / 4), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols,
-                               (const uint64_t*)nullptr, L.plan, index_col ? 0 : -1);
+            with_words(n, [&](auto w) {
+                MEL_LAUNCH(plan_masks_kernel<decltype(w)::value>, dim3((bs + 3) / 4), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols,
+                           (const uint64_t*)nullptr, L.plan, index_col ? 0 : -1);
+            });
             if (mel_status st = check_launch("plan_masks")) return st;
         }
         // fp32 + node-feature table evaluated by this call: the tuple ids and the encoder rows of the tuples are independent
@@ -940,7 +936,7 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
         a.att = w->conv1.att, a.bias = w->conv1.bias, a.adj = L.plan.adj, a.kind = MEL_CONV_GATV2;
         a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv1.channels / (hc / 64);
         a.obs = obs, a.obs_stride = obs_width, a.node_cols = node_cols, a.aggregator = aggregator;
-        a.pooled = L.xcat, a.fid = table ? L.plan.fid : nullptr, a.legacy_walk = att_legacy_walk(w);
+        a.pooled = L.xcat, a.fid = table ? L.plan.fid : nullptr;
         StageScope t(MEL_STAGE_CONV1_ATT, s);
         if (mel_status st = launch_attend<ATT_POOL>(a, hc, s, "conv1 attention + pool")) return st;
     }
@@ -1078,10 +1074,10 @@ mel_status mel_radius_graph(const float* obs, int64_t bs, int32_t n, int32_t obs
         obs_stride < n * (in_dim + 3))
         return fail(MEL_ERR_INVALID_ARG, "mel_radius_graph: bad arguments");
     clear_stale_error();
-    if (n > 64) MEL_LAUNCH(radius_graph_kernel<2>, dim3((bs + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), obs, (int)bs, n,
-                           obs_stride, in_dim + 3, adj);
-    else MEL_LAUNCH(radius_graph_kernel<1>, dim3((bs + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), obs, (int)bs, n,
-                       obs_stride, in_dim + 3, adj);
+    with_words(n, [&](auto w) {
+        MEL_LAUNCH(radius_graph_kernel<decltype(w)::value>, dim3((bs + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), obs, (int)bs, n,
+                   obs_stride, in_dim + 3, adj);
+    });
     return check_launch("mel_radius_graph");
 }
 

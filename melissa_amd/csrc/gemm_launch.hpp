@@ -24,14 +24,12 @@ namespace mel {
 // A/B switches for benchmarks and tests, read once per process: MEL_NO_PLANES_GEMM keeps conv2 off
 // gemm_planes_kernel, MEL_PLANES_FROM moves the launch size from which it is taken, MEL_NO_BF16_WIDE keeps the bf16 feature
 // path's large projections off gemm_bf16_wide_kernel, MEL_NO_FUSED_TABLE evaluates the node-feature table of a forward in two
-// launches (encoder tiles beside the row lists, then conv1's projections) instead of inside the plan launch (gemm_table.hpp),
-// MEL_ATT_LEGACY_WALK gives every forward MEL_FWD_ATT_LEGACY_WALK (attention.hpp).
-struct GemmTuning { bool no_planes; long planes_from; bool no_bf16_wide; bool no_fused_table; bool att_legacy_walk; };
+// launches (encoder tiles beside the row lists, then conv1's projections) instead of inside the plan launch (gemm_table.hpp).
+struct GemmTuning { bool no_planes; long planes_from; bool no_bf16_wide; bool no_fused_table; };
 static const GemmTuning& gemm_tuning() {
     static const GemmTuning t{getenv("MEL_NO_PLANES_GEMM") != nullptr,
                               getenv("MEL_PLANES_FROM") ? atol(getenv("MEL_PLANES_FROM")) : (long)MEL_PLANES_FROM,
-                              getenv("MEL_NO_BF16_WIDE") != nullptr, getenv("MEL_NO_FUSED_TABLE") != nullptr,
-                              getenv("MEL_ATT_LEGACY_WALK") != nullptr && atoi(getenv("MEL_ATT_LEGACY_WALK")) != 0};
+                              getenv("MEL_NO_BF16_WIDE") != nullptr, getenv("MEL_NO_FUSED_TABLE") != nullptr};
     return t;
 }
 

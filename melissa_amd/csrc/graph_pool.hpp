@@ -234,15 +234,11 @@ static mel_status launch_graph_pool(int32_t n_nodes, double radius_sq, int64_t f
     const int grid = n_candidates;
 #endif
     const dim3 wgrid((unsigned)(((int64_t)n_candidates + 3) / 4));
-    if (n_nodes > 64) {
-        MEL_LAUNCH(graph_pool_candidate_kernel<2>, dim3(grid), dim3(64), 0, stream, a);
+    with_words(n_nodes, [&](auto w) {
+        MEL_LAUNCH(graph_pool_candidate_kernel<decltype(w)::value>, dim3(grid), dim3(64), 0, stream, a);
         MEL_LAUNCH(graph_pool_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
-        MEL_LAUNCH(graph_pool_write_kernel<2>, wgrid, dim3(256), 0, stream, a);
-    } else {
-        MEL_LAUNCH(graph_pool_candidate_kernel<1>, dim3(grid), dim3(64), 0, stream, a);
-        MEL_LAUNCH(graph_pool_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
-        MEL_LAUNCH(graph_pool_write_kernel<1>, wgrid, dim3(256), 0, stream, a);
-    }
+        MEL_LAUNCH(graph_pool_write_kernel<decltype(w)::value>, wgrid, dim3(256), 0, stream, a);
+    });
     return check_launch("graph_pool_generate");
 }
 

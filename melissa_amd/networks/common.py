@@ -157,12 +157,8 @@ class HipForwardMixin:
     # every forward (it depends on the weights only).  Off by default: a forward then does all of its own arithmetic.
     prepared_tables = False
 
-    # A/B and tests: the attention launches walk their sources the former way (MEL_FWD_ATT_LEGACY_WALK) - same bits.
-    attention_legacy_walk = False
-
     def _forward_flags(self, plan_ready: bool, integer_features: bool) -> int:
-        return ((_lib.FWD_PLAN_READY if plan_ready else 0) | (_lib.FWD_INTEGER_FEATURES if integer_features else 0) |
-                (_lib.FWD_ATT_LEGACY_WALK if self.attention_legacy_walk else 0))
+        return (_lib.FWD_PLAN_READY if plan_ready else 0) | (_lib.FWD_INTEGER_FEATURES if integer_features else 0)
 
     def _refresh_tables(self, w, device):
         if not self.prepared_tables or self.input_dim != 5:
