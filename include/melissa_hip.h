@@ -82,8 +82,8 @@ typedef struct mel_gatv2 {
     mel_linear lin_r;
     const float* att;
     const float* bias;
-    int32_t heads;
-    int32_t channels;      /* C, per head */
+    int32_t heads;         /* a power of two (a head is 64 / heads lanes of a wavefront), or 6 (8 lanes per head, 48 of 64 live) */
+    int32_t channels;      /* C, per head: 2, 4, 8 or 16 per lane of its head (6 heads: 64 or 128); else MEL_ERR_UNSUPPORTED */
     mel_linear lin_v;
     int32_t kind;
     int32_t reserved;
@@ -310,7 +310,9 @@ mel_status mel_transpose_f32(const float* src, int32_t ld_src, int64_t rows, int
 
 /* ---- learn path: attention and pool with hand-written backward ---------------------------
  * Wrapped by torch.autograd.Function in melissa_amd/networks/autograd_ops.py; all buffers device fp32, row-major,
- * rows = bs * n_nodes (row b*n + i = node i of graph b), HC = heads * channels in {128, 256, 512, 1024}.
+ * rows = bs * n_nodes (row b*n + i = node i of graph b), HC = heads * channels: a head is the largest power of two of
+ * lanes with heads * lanes <= 64, of 2, 4, 8 or 16 channels each - heads a power of two (HC = 128 .. 1024), or 6 heads of 64
+ * or 128 channels (HC = 384 / 768; 48 live lanes, the other 16 touch no memory).  Rows are HC floats apart, no padding.
  *
  * mel_radius_graph: adj[b*n + i] = sources of target i ([3P] radius_graph on the fp32 obs positions,
  *   networks/common.py:47-48: strict <, first 33 hits, self excluded) - the mask the forward kernels build.

@@ -11,6 +11,8 @@ namespace mel {
 // span the heads*C output channels (VPL contiguous channels per lane, so a head is C/VPL adjacent
 // lanes and the per-head score reduction is a few xor-shuffles).  Sources are streamed once with an
 // online softmax: out = sum_j exp(e_j - m) x_l[j] / (sum_j exp(e_j - m) + 1e-16).
+// A head count that is no power of two leaves lanes over: 6 heads take 8 lanes each and lanes 48 .. 63
+// carry no channels (common.hpp: head_lanes; ATT_WALK_GENERIC_48 below).
 // ------------------------------------------------------------------------------------------------
 enum { ATT_ROWS = 0, ATT_POOL = 1, ATT_SINGLE = 2 };
 
@@ -140,6 +142,12 @@ __device__ __forceinline__ void store_row(float* base, size_t idx, const Vec<VPL
 // LPH = 16: known at compile time (no branch, no shuffle loop in the caller's step); 0: decided per call.
 template <int LPH = 0>
 __device__ __forceinline__ float head_sum(float s, int lanes_per_head) {
+    if constexpr (LPH == 8) {           // 8 lanes per head (6 heads on 48 lanes): the first three of the moves below
+        s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+        s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+        s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x141, 0xF, 0xF, true));  // row_half_mirror
+        return s;
+    }
     if (LPH == 16 || lanes_per_head == 16) {
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
@@ -170,8 +178,35 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 //   row indices from that register with v_readlane: no set arithmetic and no launch-uniform branch inside a step
 //   GENERIC  table mode and the lanes per head decided at run time (any shape)
 //   LIST_16 / TABLE_16  row-list / table mode with 16 lanes per head, both known at compile time (the headline shapes)
+//   GENERIC_48  the generic walk on a wavefront of which only 48 lanes carry channels: 6 heads of 8 lanes (common.hpp:
+//               head_lanes).  Lanes 48 .. 63 are IDLE: they hold zeros instead of row values, load and store nothing that is
+//               addressed by channel, and still serve the source list (lane k holds the k-th source, k up to 63) and the
+//               tuple ids of nodes 48 .. 63.  A head's 8 lanes never exchange anything with another head's or with idle lanes.
 // (the values are part of the kernels' mangled names, which profiles and kernel traces quote: 0 was the former walk)
-enum { ATT_WALK_GENERIC = 1, ATT_WALK_LIST_16 = 2, ATT_WALK_TABLE_16 = 3 };
+enum { ATT_WALK_GENERIC = 1, ATT_WALK_LIST_16 = 2, ATT_WALK_TABLE_16 = 3, ATT_WALK_GENERIC_48 = 4 };
+
+// lanes of a wavefront that carry channels in this form (a row is LIVE * VPL channels wide)
+template <int FORM>
+constexpr int att_live_lanes() { return FORM == ATT_WALK_GENERIC_48 ? 48 : 64; }
+
+// row loads / stores of the lanes that carry channels; an idle lane holds zeros and touches no memory.  On a full wavefront
+// these ARE load_row / store_row / load_vec.
+template <int VPL, bool BF, int LIVE>
+__device__ __forceinline__ Vec<VPL> load_row_live(const float* base, size_t idx, int lane) {
+    if constexpr (LIVE == 64) {
+        return load_row<VPL, BF>(base, idx);
+    } else {
+        Vec<VPL> r;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) r.v[i] = 0.f;
+        if (lane < LIVE) r = load_row<VPL, BF>(base, idx);
+        return r;
+    }
+}
+template <int VPL, bool BF, int LIVE>
+__device__ __forceinline__ void store_row_live(float* base, size_t idx, const Vec<VPL>& r, int lane) {
+    if (LIVE == 64 || lane < LIVE) store_row<VPL, BF>(base, idx, r);
+}
 
 template <int FORM>
 __device__ __forceinline__ bool att_table_mode(const AttArgs& a) {
@@ -256,16 +291,17 @@ template <int VPL, int KIND, bool BF, int W, int G, int FORM>
 __device__ __forceinline__ Vec<VPL> attend_target(const AttArgs& a, size_t xr_row, NodeSet<W> sources,
                                                   const NodeSet<W>& smask, int soff, const Vec<VPL>& att,
                                                   const Vec<VPL>& bias, int lane, const int (&my_fid)[W]) {
-    constexpr int HC = 64 * VPL;
+    constexpr int LIVE = att_live_lanes<FORM>();
+    constexpr int HC = LIVE * VPL;               // the row's real width: the TransformerConv value half starts there
     // G = sources per online-softmax step.  Row kernels: 2 - with 4 the kernel needs 112 VGPRs (four waves per SIMD), with 2 it
     // fits 96 (five): conv1 attention 24.3 -> 22.8 us, conv2 attention 13.4 -> 13.0 us, step 0.2180 -> 0.2142 ms (two A/B
     // pairs; 3: 24.1 us).  The HL-DGN pool kernel: 2 as well (MEL_ATT_GP: 39.9 -> 33.5 us; 1: 36.4, 3: 34.5).
-    const Vec<VPL> xr = load_row<VPL, BF>(a.xr, xr_row * a.ld_r + lane * VPL);
+    const Vec<VPL> xr = load_row_live<VPL, BF, LIVE>(a.xr, xr_row * a.ld_r + lane * VPL, lane);
     float m = -INFINITY, l = 0.f;
     Vec<VPL> acc;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) acc.v[i] = 0.f;
-    constexpr int LPH = FORM == ATT_WALK_GENERIC ? 0 : 16;
+    constexpr int LPH = FORM == ATT_WALK_GENERIC ? 0 : FORM == ATT_WALK_GENERIC_48 ? 8 : 16;
     constexpr int CHUNK = 64 - 64 % G;           // sources per list: whole steps, one lane each (the neighbour cap keeps a
                                                  // target at 34 sources, so this loop runs once; it is here for the bound)
     NodeSet<W> left = ns_uniform(sources);       // SGPRs: the list is built by scalar instructions
@@ -297,8 +333,8 @@ __device__ __forceinline__ Vec<VPL> attend_target(const AttArgs& a, size_t xr_ro
             for (int k = 0; k < G; ++k) {
                 on[k] = s0 + k < nl;             // slot 0 is always on
                 const float* src = source_row<BF>(a.xl, __builtin_amdgcn_readlane(rowv, s0 + k), a.ld_l);
-                xl[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL));
-                if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row<VPL, BF>(src, (unsigned)(lane * VPL + HC));
+                xl[k] = load_row_live<VPL, BF, LIVE>(src, (unsigned)(lane * VPL), lane);
+                if constexpr (KIND == MEL_CONV_TRANSFORMER) xv[k] = load_row_live<VPL, BF, LIVE>(src, (unsigned)(lane * VPL + HC), lane);
             }
             // every row load of the step is in flight before its arithmetic starts (left alone, the scheduler sinks the
             // second source's loads below the first source's score: one memory latency after the other).  Not for bf16 rows:
@@ -347,10 +383,10 @@ __device__ __forceinline__ void store_row_planes(uint16_t* base, int r, int K, i
     }
 }
 
-template <int VPL>
+template <int VPL, int LIVE = 64>
 __device__ __forceinline__ Vec<VPL> load_vec_or_zero(const float* p, int lane) {
     Vec<VPL> r;
-    if (p) return load_vec<VPL>(p + lane * VPL);
+    if (p && (LIVE == 64 || lane < LIVE)) return load_vec<VPL>(p + lane * VPL);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) r.v[i] = 0.f;
     return r;
@@ -392,8 +428,9 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
     const auto wave_start = prof.mark();
     const int lane = lane_id();
     const int rows = min(*a.rows_dev, a.rows_cap);
-    const Vec<VPL> att = load_vec_or_zero<VPL>(a.att, lane);
-    const Vec<VPL> bias = load_vec_or_zero<VPL>(a.bias, lane);
+    constexpr int LIVE = att_live_lanes<FORM>();
+    const Vec<VPL> att = load_vec_or_zero<VPL, LIVE>(a.att, lane);
+    const Vec<VPL> bias = load_vec_or_zero<VPL, LIVE>(a.bias, lane);
     // grid-stride over the target rows: the grid is sized from the expected row count, not the worst case
     // (a surplus workgroup costs a global-load latency and a CU slot before it can exit)
     // XCD-aware order: consecutive target rows belong to one env and share their source rows, so each XCD
@@ -423,7 +460,7 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
         const Vec<VPL> o = attend_target<VPL, KIND, BF, W, MEL_ATT_G, FORM>(a, xr_row, d.sources, d.smask, d.soff, att, bias, lane, my_fid);
         prof.lap(2, o.v[0]);
         if constexpr (MODE == ATT_SINGLE) {
-            store_row<VPL, BF>(a.xcat, (size_t)r * a.ld_cat + a.cat_off + lane * VPL, o);
+            store_row_live<VPL, BF, LIVE>(a.xcat, (size_t)r * a.ld_cat + a.cat_off + lane * VPL, o, lane);
         } else {
             Vec<VPL> om = o;
             if (a.out_scale) {
@@ -432,14 +469,14 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
                 for (int i = 0; i < VPL; ++i) om.v[i] = o.v[i] * dmv;
             }
             bool as_rows = true;
-            if constexpr (!BF && VPL % 4 == 0) {
+            if constexpr (!BF && VPL % 4 == 0 && LIVE == 64) {      // (rows narrower than the wavefront go out as fp32 rows: fwd.hip)
                 if (a.out_planes) store_row_planes<VPL>(a.out_planes, r, a.ldo, lane, om), as_rows = false;
             }
-            if (as_rows) store_row<VPL, BF>(a.out, (size_t)r * a.ldo + lane * VPL, om);
+            if (as_rows) store_row_live<VPL, BF, LIVE>(a.out, (size_t)r * a.ldo + lane * VPL, om, lane);
             if (d.cat_row >= 0) {
                 const size_t cat = (size_t)d.cat_row * a.ld_cat;
                 // x_2: the controlling agent's conv1 row BEFORE the decision-maker mask (l_dgn.py:127)
-                store_row<VPL, BF>(a.xcat, cat + a.hidden + lane * VPL, o);
+                store_row_live<VPL, BF, LIVE>(a.xcat, cat + a.hidden + lane * VPL, o, lane);
                 // x_1: its encoder row (l_dgn.py:122)
                 const size_t h0 = (size_t)(table ? node_i32<W>(my_fid, d.node) : d.soff + ns_rank_below(d.smask, d.node)) * a.hidden;
                 if constexpr (BF) {
@@ -467,13 +504,14 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
 template <int VPL, bool BF, int NW, int W, int FORM>
 __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
     const bool table = att_table_mode<FORM>(a);
-    constexpr int HC = 64 * VPL;
+    constexpr int LIVE = att_live_lanes<FORM>();
+    constexpr int HC = LIVE * VPL;
     __shared__ float part[NW][HC];
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
     const int b = blockIdx.x;
-    const Vec<VPL> att = load_vec<VPL>(a.att + lane * VPL);
-    const Vec<VPL> bias = load_vec<VPL>(a.bias + lane * VPL);
+    const Vec<VPL> att = load_row_live<VPL, false, LIVE>(a.att, lane * VPL, lane);
+    const Vec<VPL> bias = load_row_live<VPL, false, LIVE>(a.bias, lane * VPL, lane);
     const NodeSet<W> full = ns_full<W>(a.n);
     Vec<VPL> pool;
 #pragma unroll
@@ -492,8 +530,10 @@ __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
             pool.v[i] = (a.aggregator == MEL_AGG_MAX) ? fmaxf(pool.v[i], v) : pool.v[i] + v;
         }
     }
+    if (LIVE == 64 || lane < LIVE) {
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) part[wave][lane * VPL + i] = pool.v[i];
+        for (int i = 0; i < VPL; ++i) part[wave][lane * VPL + i] = pool.v[i];
+    }
     __syncthreads();
     for (int c = threadIdx.x; c < HC; c += 64 * NW) {
         float v = part[0][c];
@@ -513,7 +553,8 @@ __global__ __launch_bounds__(64 * NW) void gat_attend_pool_kernel(AttArgs a) {
 // The walk form of a launch (ATT_WALK_*).  The compile-time forms exist for 8 channels per lane with 16 lanes per head - hidden
 // size 128 with four heads, which every configuration BASELINE quotes runs at; every other shape takes the generic list walk.
 template <int V, int MODE>
-static int att_walk_form(const AttArgs& a) {
+static int att_walk_form(const AttArgs& a, int live) {
+    if (live == 48) return ATT_WALK_GENERIC_48;     // (V 8 and 16 only: head_lanes admits nothing else on 48 lanes)
     if (V == 8 && a.lanes_per_head == 16) return (MODE != ATT_SINGLE && a.fid) ? ATT_WALK_TABLE_16 : ATT_WALK_LIST_16;
     return ATT_WALK_GENERIC;
 }
@@ -543,20 +584,27 @@ static void launch_attend_form(const AttArgs& a, int grid, hipStream_t s) {
 
 // V channels per lane: the launch in the walk form of its arguments - only the forms att_walk_form can name are instantiated
 template <int V, int MODE>
-static void launch_attend_v(const AttArgs& a, int grid, hipStream_t s) {
-    switch (att_walk_form<V, MODE>(a)) {
+static bool launch_attend_v(const AttArgs& a, int live, int grid, hipStream_t s) {      // false: no such instantiation
+    switch (att_walk_form<V, MODE>(a, live)) {
         case ATT_WALK_LIST_16:
             if constexpr (V == 8) launch_attend_form<V, MODE, ATT_WALK_LIST_16>(a, grid, s);
             break;
         case ATT_WALK_TABLE_16:
             if constexpr (V == 8 && MODE != ATT_SINGLE) launch_attend_form<V, MODE, ATT_WALK_TABLE_16>(a, grid, s);
             break;
+        case ATT_WALK_GENERIC_48:
+            if constexpr (V == 8 || V == 16) launch_attend_form<V, MODE, ATT_WALK_GENERIC_48>(a, grid, s);
+            else return false;
+            break;
         default: launch_attend_form<V, MODE, ATT_WALK_GENERIC>(a, grid, s); break;
     }
+    return true;
 }
 
 template <int MODE>
-static mel_status launch_attend(const AttArgs& a, int hc, hipStream_t s, const char* what) {
+static mel_status launch_attend(AttArgs a, const HeadLanes& hl, hipStream_t s, const char* what) {
+    if (!hl.ok()) return fail(MEL_ERR_UNSUPPORTED, "%s: %s", what, hl.why);
+    a.lanes_per_head = hl.lanes_per_head;
     int grid = 0;                                       // the pool kernel: one workgroup per env
     if constexpr (MODE != ATT_POOL) {
         long want = ((a.rows_hint > 0 ? a.rows_hint : a.rows_cap) * 5 / 4 + 3) / 4;     // 25 % head-room, loop covers the rest
@@ -570,13 +618,15 @@ static mel_status launch_attend(const AttArgs& a, int hc, hipStream_t s, const c
 #endif
         grid = (int)((want + 7) & ~7L);                 // multiple of 8: block id % 8 = XCD
     }
-    switch (hc / 64) {
-        case 2: launch_attend_v<2, MODE>(a, grid, s); break;
-        case 4: launch_attend_v<4, MODE>(a, grid, s); break;
-        case 8: launch_attend_v<8, MODE>(a, grid, s); break;
-        case 16: launch_attend_v<16, MODE>(a, grid, s); break;
-        default: return fail(MEL_ERR_UNSUPPORTED, "%s: heads*C = %d not in {128,256,512,1024}", what, hc);
+    bool launched = false;
+    switch (hl.vpl) {
+        case 2: launched = launch_attend_v<2, MODE>(a, hl.live, grid, s); break;
+        case 4: launched = launch_attend_v<4, MODE>(a, hl.live, grid, s); break;
+        case 8: launched = launch_attend_v<8, MODE>(a, hl.live, grid, s); break;
+        default: launched = launch_attend_v<16, MODE>(a, hl.live, grid, s); break;
     }
+    if (!launched)
+        return fail(MEL_ERR_UNSUPPORTED, "%s: no kernel for %d channels per lane on %d live lanes", what, hl.vpl, hl.live);
     return check_launch(what);
 }
 

@@ -97,6 +97,32 @@ inline void with_flag(bool on, F&& f) {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// How the attention kernels (attention.hpp, grad.hip) lay heads x channels over a wavefront: a head is `lanes_per_head`
+// adjacent lanes - the largest power of two with heads * lanes_per_head <= 64 - of `vpl` consecutive channels each, and the
+// lanes from `live` = heads * lanes_per_head on carry no channels (6 heads: 8 lanes per head, 48 live lanes, 16 idle).
+// The kernels exist for vpl 2, 4, 8, 16 on a full wavefront and for vpl 8, 16 on 48 live lanes; `why` names the rule a
+// refused shape breaks (the ONE statement of it: validate(), check_gat and the launches all ask here, and
+// melissa_amd.networks.hip_shape_supported restates it in Python).
+struct HeadLanes {
+    int lanes_per_head = 0, live = 0, vpl = 0;
+    const char* why = nullptr;          // null: the shape runs
+    bool ok() const { return why == nullptr; }
+};
+inline HeadLanes head_lanes(int heads, int channels) {
+    HeadLanes h;
+    if (heads < 1 || heads > 64 || channels < 1) return h.why = "heads outside [1, 64] or no channels", h;
+    h.lanes_per_head = 1;
+    while (heads * h.lanes_per_head * 2 <= 64) h.lanes_per_head *= 2;
+    h.live = heads * h.lanes_per_head;
+    if (channels % h.lanes_per_head) return h.why = "channels per head must be a multiple of the lanes per head (largest power of two with heads * lanes <= 64)", h;
+    h.vpl = channels / h.lanes_per_head;
+    if (h.vpl != 2 && h.vpl != 4 && h.vpl != 8 && h.vpl != 16)
+        return h.why = "channels per lane (channels / lanes per head) must be 2, 4, 8 or 16", h;
+    if (h.live != 64 && !(h.live == 48 && h.lanes_per_head == 8 && h.vpl >= 8))
+        return h.why = "heads must be a power of two (a full wavefront), or 6 with 64 or 128 channels (48 live lanes)", h;
+    return h;
+}
+
 // Bump allocator over the caller-provided workspace (256-byte granules).
 struct Carver {
     char* base;

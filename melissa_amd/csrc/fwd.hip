@@ -48,6 +48,47 @@ __global__ __launch_bounds__(256, 2) void fid_enc_kernel(const float* __restrict
     else feature_ids_body(obs, bs, n, obs_stride, node_cols, p, table_rows, (int)blockIdx.x - gemm_blocks);
 }
 
+// Encoder layer 0 on its own, for encoders WIDER than the GEMMs' fused producer stages (ENC_FUSED_MAX_K columns of layer-0
+// weights in LDS: hidden 512).  A0[m, k] = relu(enc_b[k] + sum_f enc_w[k, f] x_f(m)) in the producer's arithmetic (fetch_a<ENC>),
+// fp32 rows or - bf16 feature path - bf16 rows; the encoder's second layer then is a PLAIN GEMM on A0 (launch_encoder).
+// One wavefront per row, a lane per column; rows by the device-side count where the problem has one.
+constexpr int ENC_FUSED_MAX_K = 256;         // = ENC_MAX_K of the GEMM kernels
+constexpr int ENC_MAX_WIDTH = 512;
+__global__ __launch_bounds__(256) void encoder_layer0_kernel(GemmArgs g, float* A0, int as_bf16) {
+    const int M = gemm_rows(g);
+    const int lane = lane_id();
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += gridDim.x * 4) {
+        float x[8];
+        enc_features(g, row, x);
+        for (int k = lane; k < g.K; k += 64) {
+            float v = g.enc_b[k];
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                if (f < g.in_dim) v = fmaf(g.enc_w[(size_t)k * g.in_dim + f], x[f], v);
+            v = fmaxf(v, 0.f);
+            if (as_bf16) reinterpret_cast<uint16_t*>(A0)[(size_t)row * g.K + k] = (uint16_t)pack_bf16x2(v, 0.f);
+            else A0[(size_t)row * g.K + k] = v;
+        }
+    }
+}
+
+// The encoder launch of problem g (an ENC-mode problem: obs / nid or feat_domain, enc_w, enc_b): the GEMM's fused producer
+// where the encoder fits it, else layer 0 into `scratch` (g.M rows of g.K values) and a PLAIN GEMM on those rows.
+static mel_status launch_encoder(GemmArgs g, float* scratch, hipStream_t s, const char* what, long m_hint = -1) {
+    if (g.K <= ENC_FUSED_MAX_K) return launch_gemm(g, GEMM_MODE_ENC, s, what, m_hint);
+    if (!scratch) return fail(MEL_ERR_WORKSPACE, "%s: no scratch for the rows of an encoder %d wide", what, g.K);
+    if (g.M <= 0) return MEL_OK;
+    long rows = m_hint > 0 && m_hint < g.M ? m_hint : g.M;
+    int grid = (int)((rows + 3) / 4);
+    grid = grid < 1 ? 1 : grid > 8192 ? 8192 : grid;
+    MEL_LAUNCH(encoder_layer0_kernel, dim3(grid), dim3(256), 0, s, g, scratch, g.bf16);
+    if (mel_status st = check_launch(what)) return st;
+    g.A = scratch, g.lda = g.K, g.arow = nullptr;
+    g.obs = nullptr, g.nid = nullptr, g.feat_domain = 0;
+    return launch_gemm(g, GEMM_MODE_PLAIN, s, what, m_hint);
+}
+static bool encoder_fuses(const mel_weights* w) { return w->encoder.layer[0].out_dim <= ENC_FUSED_MAX_K; }
+
 // ------------------------------------------------------------------------------------------------
 // workspace layout
 // ------------------------------------------------------------------------------------------------
@@ -79,6 +120,7 @@ struct FwdLayout {
     float* hq[2];   // head hidden ping-pong [rows, qw + vw]
     float* hpart;   // split-K partial planes of the heads' first layer [HEAD_KSPLIT_MAX][rows, qw + vw] (fp32 path)
     float* minmax;
+    float* enc0;    // encoder layer-0 rows, only for encoders wider than the GEMMs' fused producer (launch_encoder), else null
     uint16_t* wb;   // bf16 copies of the projection weights (bf16 feature path)
     size_t wb_elems;
     size_t bytes;
@@ -97,6 +139,23 @@ struct ProjWeights {
     const float* v[MEL_MAX_HEAD_LAYERS];
     const ProjWeights* alt;        // MEL_PREC_F32_AUTO: the same matrices as bf16 planes (the slots above hold the fp32 ones)
 };
+
+// MEL_PREC_F32_SPLIT: the split kernels stage K in steps that need K >= 128 (check_gemm_shape).  A projection with a shorter K
+// (hidden 64: the encoder's second layer and conv1; 64-wide dueling layers) keeps its fp32 matrix and runs on the exact-fp32
+// kernels - the same fp32-accurate result.  resolve_projections and every launch site decide by this one rule.
+// Layer i >= 1 of the Q head and of the V head share ONE launch (run_heads): the two are split together or not at all, by the
+// shorter K of the pair, so that no launch ever mixes an fp32 matrix with bf16 planes.
+constexpr int SPLIT_MIN_K = 128;
+static int split_k(int sp, int K) { return sp && K >= SPLIT_MIN_K; }
+static bool split_keeps_fp32(const mel_weights* w, const mel_linear& l) {
+    if (l.in_dim < SPLIT_MIN_K) return true;
+    if (!w->dueling) return false;
+    for (int i = 0; i < w->q_head.n_layers && i < w->v_head.n_layers; ++i) {
+        if (&l == &w->q_head.layer[i]) return w->v_head.layer[i].in_dim < SPLIT_MIN_K;
+        if (&l == &w->v_head.layer[i]) return w->q_head.layer[i].in_dim < SPLIT_MIN_K;
+    }
+    return false;
+}
 
 static bool has_planes(const mel_weights* w) { return w->precision == MEL_PREC_F32_SPLIT || w->precision == MEL_PREC_F32_AUTO; }
 static size_t lin_elems(const mel_linear& l) { return l.weight ? (size_t)l.in_dim * l.out_dim : 0; }
@@ -205,6 +264,9 @@ static FwdLayout carve(const mel_weights* w, const Dims& d, void* ws) {
     L.wb_elems = (w->precision == MEL_PREC_BF16) ? projection_elems(w) : has_planes(w) ? plane_elems(w) : 0;
     if (w->prepared) L.wb_elems = 0;             // the caller holds the converted weights (mel_prepare_weights)
     L.wb = c.take<uint16_t>(L.wb_elems ? L.wb_elems : 8);
+    // (taken last, and only for a wide encoder: every other shape keeps its layout)
+    L.enc0 = encoder_fuses(w) ? nullptr
+                              : c.take<float>((w->model != MEL_MODEL_HLDGN ? rows2 : rowsM) * (size_t)w->encoder.layer[0].out_dim);
     L.bytes = c.off;
     L.rows_cap = R;
     return L;
@@ -228,16 +290,13 @@ static mel_status validate(const mel_weights* w, int model, int64_t bs, int n, i
     const int hidden = w->encoder.layer[1].out_dim;
     if (w->encoder.layer[0].in_dim != w->in_dim || w->encoder.layer[1].in_dim != w->encoder.layer[0].out_dim)
         return fail(MEL_ERR_INVALID_ARG, "encoder layer shapes inconsistent");
-    if (w->encoder.layer[0].out_dim > 256)
-        return fail(MEL_ERR_UNSUPPORTED, "encoder hidden width %d > 256", w->encoder.layer[0].out_dim);
+    if (w->encoder.layer[0].out_dim > ENC_MAX_WIDTH)
+        return fail(MEL_ERR_UNSUPPORTED, "encoder hidden width %d > %d", w->encoder.layer[0].out_dim, ENC_MAX_WIDTH);
     if (w->encoder.layer[0].out_dim % 32 || hidden % 64)
         return fail(MEL_ERR_UNSUPPORTED, "encoder widths must be multiples of 64 (got %d, %d)", w->encoder.layer[0].out_dim, hidden);
     const int hc = w->conv1.heads * w->conv1.channels;
-    if (hc != 128 && hc != 256 && hc != 512 && hc != 1024)
-        return fail(MEL_ERR_UNSUPPORTED, "heads*channels = %d not in {128,256,512,1024}", hc);
-    const int lph = hc / 64 ? w->conv1.channels / (hc / 64) : 0;
-    if (lph < 1 || (lph & (lph - 1)) || lph * (hc / 64) != w->conv1.channels)
-        return fail(MEL_ERR_UNSUPPORTED, "channels per head (%d) must be a power-of-two multiple of %d", w->conv1.channels, hc / 64);
+    if (const HeadLanes hl = head_lanes(w->conv1.heads, w->conv1.channels); !hl.ok())
+        return fail(MEL_ERR_UNSUPPORTED, "%d heads of %d channels: %s", w->conv1.heads, w->conv1.channels, hl.why);
     if (w->conv1.lin_l.in_dim != hidden || w->conv1.lin_l.out_dim != hc || w->conv1.lin_r.out_dim != hc)
         return fail(MEL_ERR_INVALID_ARG, "conv1 projection shapes inconsistent");
     const int want_kind = (model == MEL_MODEL_DGNR) ? MEL_CONV_TRANSFORMER : MEL_CONV_GATV2;
@@ -292,6 +351,7 @@ static mel_status resolve_projections(const mel_weights* w, uint16_t* dst, ProjW
         bool bad = false;
         for_each_projection(w, planes, [&](const mel_linear& l, const float** slot) {
             const size_t cnt = lin_elems(l);
+            if (!both && l.weight && split_keeps_fp32(w, l)) { *slot = l.weight; return; }     // (split_k: stays fp32)
             if (b.n >= CVT_MAX_SEG || cnt % 8 != 0 || l.in_dim % 32 != 0 || !l.weight) { bad = true; return; }
             b.src[b.n] = l.weight, b.dst[b.n] = dst + off, b.count[b.n] = (int)cnt, b.K[b.n] = l.in_dim, b.start[b.n] = blocks;
             b.rb[b.n] = 0;
@@ -437,7 +497,7 @@ static mel_status run_heads(const mel_weights* w, const ProjWeights& pw, const F
             g[1].A = in_v, g[1].lda = ld_v, g[1].W = pw.v[i], g[1].bias = v.bias;
             g[1].Y = out32 ? out + q.out_dim : reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(out) + q.out_dim);
             g[1].ldy = ldo, g[1].M = (int)rows, g[1].M_dev = rows_dev, g[1].N = v.out_dim, g[1].K = v.in_dim, g[1].relu = 1;
-            g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = sp, g[0].y_f32 = g[1].y_f32 = (bf && out32);
+            g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = split_k(sp, q.in_dim < v.in_dim ? q.in_dim : v.in_dim), g[0].y_f32 = g[1].y_f32 = (bf && out32);
             (void)in16;
             const long hints[2] = {rows_hint, rows_hint};
             if (mel_status st = launch_gemm_group(g, hints, w->dueling ? 2 : 1, s, "Q + V hidden", 3)) return st;
@@ -499,7 +559,7 @@ static TableArgs fused_table_args(const mel_weights* w, const ProjWeights& pw, i
 }
 
 static mel_status run_feature_tables(const mel_weights* w, const ProjWeights& pw, int n, const FeatureTables& t, hipStream_t s,
-                                     bool encoder_done = false) {
+                                     bool encoder_done = false, float* enc0 = nullptr) {
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
     const int hidden = w->encoder.layer[1].out_dim, hc = w->conv1.heads * w->conv1.channels;
     const int bf = w->precision == MEL_PREC_BF16, sp = w->precision == MEL_PREC_F32_SPLIT;
@@ -507,25 +567,33 @@ static mel_status run_feature_tables(const mel_weights* w, const ProjWeights& pw
     if (!encoder_done) {
         GemmArgs g;
         g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = sp;
+        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
         // bf16 feature path: the table's encoder rows come from the exact-fp32 tile on the fp32 weights, stored as bf16 - the form
         // the forward's fused launch (plan_enc_kernel / fid_enc_kernel) evaluates, so prepared and per-call tables are identical
         if (bf) g.W = w->encoder.layer[1].weight, g.bf16 = 0, g.y_bf16 = 1;
         g.Y = t.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
         StageScope sc(MEL_STAGE_ENCODER, s);
-        if (mel_status st = launch_gemm(g, GEMM_MODE_ENC, s, "encoder (feature tuples)", T)) return st;
+        // a wide encoder without scratch of the caller's (the prepared tables): its layer-0 rows pass through t.xl, which the
+        // projections below write only after the encoder has read them - where they fit
+        if (!enc0 && !encoder_fuses(w)) {
+            const size_t srcw = hl ? 2 * (size_t)hc : (tconv ? 2 * (size_t)hc : (size_t)hc);
+            if (srcw * table_elem_bytes(w) < (size_t)g.K * (g.bf16 ? 2 : 4))
+                return fail(MEL_ERR_UNSUPPORTED, "feature tables: an encoder %d wide needs rows of %d bytes, the table's are narrower", g.K, g.K * 4);
+            enc0 = t.xl;
+        }
+        if (mel_status st = launch_encoder(g, enc0, s, "encoder (feature tuples)", T)) return st;
     }
     StageScope sc(MEL_STAGE_CONV1_LIN, s);
     if (hl) {
         GemmArgs g;
-        g.A = t.h0, g.lda = hidden, g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = sp;
+        g.A = t.h0, g.lda = hidden, g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = split_k(sp, hidden);
         g.bias = w->conv1.lin_l.bias, g.bias_hi = w->conv1.lin_r.bias, g.split_n = hc;
         g.Y = t.xl, g.ldy = 2 * hc, g.M = T, g.N = 2 * hc, g.K = hidden;
         return launch_gemm(g, GEMM_MODE_PLAIN, s, "conv1.lin_l|lin_r (feature tuples)");
     }
     const int srcw = tconv ? 2 * hc : hc;
     GemmArgs g[2];
-    g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = sp;
+    g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = split_k(sp, hidden);
     g[0].A = t.h0, g[0].lda = hidden, g[0].W = pw.c1l, g[0].bias = w->conv1.lin_l.bias;
     g[0].Y = t.xl, g[0].ldy = srcw, g[0].M = T, g[0].N = srcw, g[0].K = hidden;
     if (tconv) g[0].W_hi = pw.c1v, g[0].bias_hi = w->conv1.lin_v.bias, g[0].split_n = hc;
@@ -589,7 +657,10 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     GemmRequest c2_rq;
     c2_rq.group = true;
     PlaneBlocks c2_blocks[2];
-    if (planes && hc % 4 == 0 && hc / 64 >= 4) {      // (the forms of h1 the conv1 attention can store as planes)
+    // (the forms of h1 the conv1 attention can store as planes: 4+ channels per lane on a full wavefront - rows of 6 heads,
+    //  384 or 768 wide, stay fp32 rows, so the planner is never offered the plane blocks for them)
+    const HeadLanes hl1 = head_lanes(w->conv1.heads, w->conv1.channels);
+    if (planes && hl1.live == 64 && hl1.vpl >= 4) {
         c2_blocks[0] = {planes->c2l_blk, tconv ? planes->c2v_blk : nullptr}, c2_blocks[1] = {planes->c2r_blk, nullptr};
         c2_rq.blocks = c2_blocks;
     }
@@ -615,7 +686,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         //  2 000 tuples alone took 15 us)
         // ... and where table_fused_tile fits, the same workgroups run conv1's projections of their encoder rows: the whole
         // table inside this launch
-        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n);
+        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n) && encoder_fuses(w);
         fused_table = fused_enc && table_fuses(w) && !gemm_tuning().no_fused_table;
         const PlanListsArgs pa{obs, (int)bs, n, obs_stride, node_cols, L.plan, row_offsets_out, tconv ? 0 : 1, inline_scan, table ? T : 0};
         if (fused_table) {
@@ -644,23 +715,23 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         GemmArgs g;
         g.obs = obs, g.obs_width = obs_stride, g.n_nodes = n, g.in_dim = w->in_dim, g.node_cols = node_cols;
         g.nid = L.plan.nid2, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = sp;
+        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
         g.Y = L.h0, g.ldy = hidden, g.M = U2, g.M_dev = n2, g.N = hidden;
         g.K = w->encoder.layer[0].out_dim, g.relu = 1;
         StageScope t(MEL_STAGE_ENCODER, s);
         if (!table)
-            if (mel_status st = launch_gemm(g, GEMM_MODE_ENC, s, "encoder", hint2)) return st;
+            if (mel_status st = launch_encoder(g, L.enc0, s, "encoder", hint2)) return st;
     }
     // table mode: one row per feature tuple, evaluated here (every call) unless the caller prepared them for these weights
     FeatureTables ft{L.h0, L.xl1, L.xr1};
     if (table) {
         if (w->tables && w->tables_nodes == n) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
         else if (fused_table) {}        // the plan launch made all three
-        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc)) return st;
+        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
     }
     {   // conv1.lin_l on the U2 rows + conv1.lin_r on the U1 rows, one grouped launch
         GemmArgs g[2];
-        g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = sp;
+        g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = split_k(sp, hidden);
         g[0].A = L.h0, g[0].lda = hidden, g[0].W = pw.c1l, g[0].bias = w->conv1.lin_l.bias;
         g[0].Y = L.xl1, g[0].ldy = srcw, g[0].M = U2, g[0].M_dev = n2, g[0].N = srcw, g[0].K = hidden;
         if (tconv)       // key | value of the sources in one problem (weights split along n)
@@ -679,13 +750,12 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.kind = w->conv1.kind, a.score_scale = 1.0f / sqrtf((float)w->conv1.channels), a.bf16 = bf;
         a.adj = L.plan.adj, a.bs = (int)bs, a.n = n;
         a.desc = L.plan.desc1, a.rows_dev = n1, a.rows_cap = U1, a.rows_hint = hint1;
-        a.lanes_per_head = w->conv1.channels / (hc / 64);
         a.out = L.h1, a.ldo = hc, a.xcat = L.xcat, a.ld_cat = latent, a.hidden = hidden, a.h0 = ft.h0;
         if (conv2.kernel == GemmKernel::PLANES) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
         a.out_scale = L.plan.dm1;       // the decision-maker mask (l_dgn.py:128) is applied as h1 is stored; x_2 is taken before it
         a.fid = table ? L.plan.fid : nullptr;
         StageScope t(MEL_STAGE_CONV1_ATT, s);
-        if (mel_status st = launch_attend<ATT_ROWS>(a, hc, s, "conv1 attention")) return st;
+        if (mel_status st = launch_attend<ATT_ROWS>(a, head_lanes(w->conv1.heads, w->conv1.channels), s, "conv1 attention")) return st;
     }
     {   // conv2.lin_l on the U1 rows + conv2.lin_r on the agent rows, one grouped launch
         StageScope t(MEL_STAGE_CONV2_LIN, s);
@@ -696,11 +766,11 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
         a.xl = L.xl2, a.ld_l = srcw, a.xr = L.xr2, a.ld_r = hc, a.att = w->conv2.att, a.bias = w->conv2.bias;
         a.kind = w->conv2.kind, a.score_scale = 1.0f / sqrtf((float)w->conv2.channels), a.bf16 = bf;
         a.adj = L.plan.adj;
-        a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv2.channels / (hc / 64);
+        a.bs = (int)bs, a.n = n;
         a.desc = L.plan.desc2, a.rows_dev = nL, a.rows_cap = R, a.rows_hint = hintL;
         a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc;
         StageScope t(MEL_STAGE_CONV2_ATT, s);
-        if (mel_status st = launch_attend<ATT_SINGLE>(a, hc, s, "conv2 attention")) return st;
+        if (mel_status st = launch_attend<ATT_SINGLE>(a, head_lanes(w->conv2.heads, w->conv2.channels), s, "conv2 attention")) return st;
     }
     return run_heads(w, pw, L, R, nL, hintL, logits, s, select);
 }
@@ -885,7 +955,7 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
         }
         // fp32 + node-feature table evaluated by this call: the tuple ids and the encoder rows of the tuples are independent
         // (the table depends on the weights only) - one launch runs both, as plan_enc_kernel does for L-DGN
-        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n);
+        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n) && encoder_fuses(w);
         if (fused_enc) {
             GemmArgs g;
             g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
@@ -908,16 +978,16 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
         GemmArgs g;
         g.obs = obs, g.obs_width = obs_width, g.n_nodes = n, g.in_dim = w->in_dim, g.node_cols = node_cols;
         g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = sp;
+        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
         g.Y = L.h0, g.ldy = hidden, g.M = M, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
         StageScope t(MEL_STAGE_ENCODER, s);
         if (!table)
-            if (mel_status st = launch_gemm(g, GEMM_MODE_ENC, s, "encoder")) return st;
+            if (mel_status st = launch_encoder(g, L.enc0, s, "encoder")) return st;
     }
     {   // x_l | x_r for every node in one GEMM (weights split along n)
         GemmArgs g;
         g.A = L.h0, g.lda = hidden;
-        g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = sp;
+        g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = split_k(sp, hidden);
         g.bias = w->conv1.lin_l.bias, g.bias_hi = w->conv1.lin_r.bias, g.split_n = hc;
         g.Y = L.xl1, g.ldy = 2 * hc, g.M = M, g.N = 2 * hc, g.K = hidden;
         StageScope t(MEL_STAGE_CONV1_LIN, s);
@@ -927,18 +997,18 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
     FeatureTables ft{L.h0, L.xl1, nullptr};
     if (table) {
         if (w->tables && w->tables_nodes == n) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
-        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc)) return st;
+        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
     }
     {
         AttArgs a{};
         a.xl = ft.xl, a.ld_l = 2 * hc, a.ld_r = 2 * hc, a.bf16 = bf;
         a.xr = bf ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(ft.xl) + hc) : ft.xl + hc;
         a.att = w->conv1.att, a.bias = w->conv1.bias, a.adj = L.plan.adj, a.kind = MEL_CONV_GATV2;
-        a.bs = (int)bs, a.n = n, a.lanes_per_head = w->conv1.channels / (hc / 64);
+        a.bs = (int)bs, a.n = n;
         a.obs = obs, a.obs_stride = obs_width, a.node_cols = node_cols, a.aggregator = aggregator;
         a.pooled = L.xcat, a.fid = table ? L.plan.fid : nullptr;
         StageScope t(MEL_STAGE_CONV1_ATT, s);
-        if (mel_status st = launch_attend<ATT_POOL>(a, hc, s, "conv1 attention + pool")) return st;
+        if (mel_status st = launch_attend<ATT_POOL>(a, head_lanes(w->conv1.heads, w->conv1.channels), s, "conv1 attention + pool")) return st;
     }
     return run_heads(w, pw, L, bs, nullptr, bs, logits, s, select);
 }

@@ -291,9 +291,9 @@ static GemmPlan plan_gemm(const GemmArgs* gs, const long* hints, int count, cons
         }
         if (alt && split_big_fits(t, count, GEMM_MODE_PLAIN)) return choose(p, GemmKernel::SPLIT_BIG, GEMM_MODE_PLAIN, t, count);
     }
-    if (rq.group && (g.split || g.bf16))
+    if (rq.group)       // (whichever member comes first: the kernels below read every W of a launch in ONE format)
         for (int i = 1; i < count; ++i)
-            if (g.split ? !a[i].split : !a[i].bf16) return p.reject(MEL_ERR_INVALID_ARG, "mixed precisions in one group");
+            if (!a[i].split != !g.split || !a[i].bf16 != !g.bf16) return p.reject(MEL_ERR_INVALID_ARG, "mixed precisions in one group");
 
     if (g.split) {      // a persistent 64 x 64 kernel for small launches, 128 x 128 tiles from MEL_SPLIT_BIG_FROM expected tiles on
         if (force == MEL_TILE_WIDE) {

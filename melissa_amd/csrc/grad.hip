@@ -12,7 +12,8 @@
 //                  d att += d e_ij * leaky(z),     d bias += g
 //     Transformer  d q[i] += d e_ij k[j] / sqrt(C),  d k[j] += d e_ij q[i] / sqrt(C),  d v[j] += alpha_ij g
 //
-// One wavefront per row, 64 lanes x VPL channels = heads x C (same mapping as the inference kernels of fwd.hip).  The
+// One wavefront per row, LIVE lanes x VPL channels = heads x C (same mapping as the inference kernels of fwd.hip; LIVE = 64
+// but for 6 heads, which fill 48 lanes: the lanes from LIVE on hold zeros and touch no memory, common.hpp: head_lanes).  The
 // backward stores no per-edge coefficient and uses NO atomics on the row gradients:
 //   targets kernel  (a wave per target i)  three passes over i's source rows - softmax statistics m_i, 1 / l_i; S_i; then
 //                   d x_r[i] (d q[i]), d att, d bias - and the three per-head scalars go to `stats`;
@@ -57,6 +58,24 @@ __device__ __forceinline__ void gstore(float* p, const GVec<VPL>& r) {
 #pragma unroll
         for (int i = 0; i < VPL; ++i) p[i] = r.v[i];
     }
+}
+
+// the lanes that carry channels load / store; an idle lane (LIVE < 64 only) holds zeros and touches no memory
+template <int VPL, int LIVE>
+__device__ __forceinline__ GVec<VPL> gload_live(const float* p, int lane) {
+    if constexpr (LIVE == 64) {
+        return gload<VPL>(p);
+    } else {
+        GVec<VPL> r;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) r.v[i] = 0.f;
+        if (lane < LIVE) r = gload<VPL>(p);
+        return r;
+    }
+}
+template <int VPL, int LIVE>
+__device__ __forceinline__ void gstore_live(float* p, const GVec<VPL>& r, int lane) {
+    if (LIVE == 64 || lane < LIVE) gstore<VPL>(p, r);
 }
 
 // sum over the lanes of one head (lanes_per_head adjacent lanes, a power of two)
@@ -115,9 +134,9 @@ __device__ __forceinline__ NodeSet<2> sources_of(const GradArgs& a, int r) {
     return m;
 }
 
-template <int VPL, int KIND>
+template <int VPL, int KIND, int LIVE>
 __global__ __launch_bounds__(256) void gat_full_forward_kernel(GradArgs a) {
-    constexpr int HC = 64 * VPL;
+    constexpr int HC = LIVE * VPL;
     const int lane = lane_id();
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.rows) return;
@@ -125,21 +144,21 @@ __global__ __launch_bounds__(256) void gat_full_forward_kernel(GradArgs a) {
     GVec<VPL> att, bias;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) att.v[i] = 0.f, bias.v[i] = 0.f;
-    if (KIND == MEL_CONV_GATV2) att = gload<VPL>(a.att + lane * VPL);
-    if (a.bias) bias = gload<VPL>(a.bias + lane * VPL);
-    const GVec<VPL> xr = gload<VPL>(a.xr + (size_t)r * HC + lane * VPL);
+    if (KIND == MEL_CONV_GATV2) att = gload_live<VPL, LIVE>(a.att + lane * VPL, lane);
+    if (a.bias) bias = gload_live<VPL, LIVE>(a.bias + lane * VPL, lane);
+    const GVec<VPL> xr = gload_live<VPL, LIVE>(a.xr + (size_t)r * HC + lane * VPL, lane);
     float m = -INFINITY, l = 0.f;
     GVec<VPL> acc;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) acc.v[i] = 0.f;
     for (NodeSet<2> s = sources_of<KIND>(a, r); ns_any(s); ns_clear_lowest(s)) {
         const size_t row = (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL;
-        const GVec<VPL> xl = gload<VPL>(a.xl + row);
+        const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + row, lane);
         const float e = edge_score<VPL, KIND>(a, xr, xl, att);
         const float mn = fmaxf(m, e);
         const float rs = expf(m - mn), pe = expf(e - mn);
         l = l * rs + pe;
-        const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload<VPL>(a.xv + row);
+        const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload_live<VPL, LIVE>(a.xv + row, lane);
 #pragma unroll
         for (int i = 0; i < VPL; ++i) acc.v[i] = fmaf(pe, sv.v[i], acc.v[i] * rs);
         m = mn;
@@ -148,24 +167,24 @@ __global__ __launch_bounds__(256) void gat_full_forward_kernel(GradArgs a) {
     GVec<VPL> o;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) o.v[i] = fmaxf(acc.v[i] * inv + bias.v[i], 0.f);
-    gstore<VPL>(a.out + (size_t)r * HC + lane * VPL, o);
+    gstore_live<VPL, LIVE>(a.out + (size_t)r * HC + lane * VPL, o, lane);
 }
 
-template <int VPL, int KIND>
+template <int VPL, int KIND, int LIVE>
 __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
-    constexpr int HC = 64 * VPL;
+    constexpr int HC = LIVE * VPL;
     const int lane = lane_id();
     GVec<VPL> att, datt, dbias;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) att.v[i] = 0.f, datt.v[i] = 0.f, dbias.v[i] = 0.f;
-    if (KIND == MEL_CONV_GATV2) att = gload<VPL>(a.att + lane * VPL);
+    if (KIND == MEL_CONV_GATV2) att = gload_live<VPL, LIVE>(a.att + lane * VPL, lane);
     for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < a.rows; r += gridDim.x * 4) {
         const int g0 = (r / a.n) * a.n;
         const size_t me = (size_t)r * HC + lane * VPL;
-        const GVec<VPL> xr = gload<VPL>(a.xr + me);
-        GVec<VPL> g = gload<VPL>(a.gout + me);
+        const GVec<VPL> xr = gload_live<VPL, LIVE>(a.xr + me, lane);
+        GVec<VPL> g = gload_live<VPL, LIVE>(a.gout + me, lane);
         {
-            const GVec<VPL> o = gload<VPL>(a.out + me);
+            const GVec<VPL> o = gload_live<VPL, LIVE>(a.out + me, lane);
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
                 g.v[i] = o.v[i] > 0.f ? g.v[i] : 0.f;          // relu'
@@ -176,7 +195,7 @@ __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
         // pass 1: softmax statistics
         float m = -INFINITY, l = 0.f;
         for (NodeSet<2> s = src; ns_any(s); ns_clear_lowest(s)) {
-            const GVec<VPL> xl = gload<VPL>(a.xl + (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL);
+            const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL, lane);
             const float e = edge_score<VPL, KIND>(a, xr, xl, att);
             const float mn = fmaxf(m, e);
             l = l * expf(m - mn) + expf(e - mn);
@@ -187,9 +206,9 @@ __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
         float S = 0.f;
         for (NodeSet<2> s = src; ns_any(s); ns_clear_lowest(s)) {
             const size_t row = (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL;
-            const GVec<VPL> xl = gload<VPL>(a.xl + row);
+            const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + row, lane);
             const float alpha = expf(edge_score<VPL, KIND>(a, xr, xl, att) - m) * inv;
-            const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload<VPL>(a.xv + row);
+            const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload_live<VPL, LIVE>(a.xv + row, lane);
             float d = 0.f;
 #pragma unroll
             for (int i = 0; i < VPL; ++i) d = fmaf(g.v[i], sv.v[i], d);
@@ -201,9 +220,9 @@ __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
         for (int i = 0; i < VPL; ++i) dxr.v[i] = 0.f;
         for (NodeSet<2> s = src; ns_any(s); ns_clear_lowest(s)) {
             const size_t row = (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL;
-            const GVec<VPL> xl = gload<VPL>(a.xl + row);
+            const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + row, lane);
             const float alpha = expf(edge_score<VPL, KIND>(a, xr, xl, att) - m) * inv;
-            const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload<VPL>(a.xv + row);
+            const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload_live<VPL, LIVE>(a.xv + row, lane);
             float d = 0.f;
 #pragma unroll
             for (int i = 0; i < VPL; ++i) d = fmaf(g.v[i], sv.v[i], d);
@@ -222,8 +241,8 @@ __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
                 for (int i = 0; i < VPL; ++i) dxr.v[i] = fmaf(des, xl.v[i], dxr.v[i]);
             }
         }
-        gstore<VPL>(a.dxr + me, dxr);
-        if (lane % a.lanes_per_head == 0) {                   // the head's three scalars (equal in all of its lanes)
+        gstore_live<VPL, LIVE>(a.dxr + me, dxr, lane);
+        if (lane % a.lanes_per_head == 0 && (LIVE == 64 || lane < LIVE)) {      // the head's three scalars (equal in all of its lanes)
             float* st = a.stats + ((size_t)r * a.heads + lane / a.lanes_per_head) * 4;
             st[0] = m, st[1] = inv, st[2] = S;
         }
@@ -235,7 +254,8 @@ __global__ __launch_bounds__(256) void gat_backward_targets_kernel(GradArgs a) {
     __shared__ float red[4][2][HC];
     const int w = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) red[w][0][lane * VPL + i] = datt.v[i], red[w][1][lane * VPL + i] = dbias.v[i];
+    for (int i = 0; i < VPL; ++i)
+        if (LIVE == 64 || lane < LIVE) red[w][0][lane * VPL + i] = datt.v[i], red[w][1][lane * VPL + i] = dbias.v[i];
     __syncthreads();
     for (int c = threadIdx.x; c < 2 * HC; c += 256) {
         const int which = c / HC, k = c - which * HC;
@@ -256,9 +276,9 @@ __global__ __launch_bounds__(256) void gat_reduce_partials_kernel(const float* _
 }
 
 // gradient of the SOURCE rows: d x_l[j] (GATv2) / d k[j], d v[j] (TransformerConv), one wave per source row j
-template <int VPL, int KIND>
+template <int VPL, int KIND, int LIVE>
 __global__ __launch_bounds__(256) void gat_backward_sources_kernel(GradArgs a) {
-    constexpr int HC = 64 * VPL;
+    constexpr int HC = LIVE * VPL;
     const int lane = lane_id();
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= a.rows) return;
@@ -267,10 +287,10 @@ __global__ __launch_bounds__(256) void gat_backward_sources_kernel(GradArgs a) {
     GVec<VPL> att;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) att.v[i] = 0.f;
-    if (KIND == MEL_CONV_GATV2) att = gload<VPL>(a.att + lane * VPL);
+    if (KIND == MEL_CONV_GATV2) att = gload_live<VPL, LIVE>(a.att + lane * VPL, lane);
     const size_t me = (size_t)r * HC + lane * VPL;
-    const GVec<VPL> xl = gload<VPL>(a.xl + me);                                     // x_l[j] / k[j]
-    const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload<VPL>(a.xv + me);     // what the targets aggregate: x_l[j] / v[j]
+    const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + me, lane);                                     // x_l[j] / k[j]
+    const GVec<VPL> sv = (KIND == MEL_CONV_GATV2) ? xl : gload_live<VPL, LIVE>(a.xv + me, lane);     // what the targets aggregate: x_l[j] / v[j]
     GVec<VPL> acc_l, acc_v;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) acc_l.v[i] = 0.f, acc_v.v[i] = 0.f;
@@ -280,15 +300,16 @@ __global__ __launch_bounds__(256) void gat_backward_sources_kernel(GradArgs a) {
         const bool reads_j = ((word >> (jn & 63)) & 1ull) || (KIND == MEL_CONV_GATV2 && t == jn);   // GATv2: self-loop
         if (!reads_j) continue;
         const size_t ti_off = (size_t)ti * HC + lane * VPL;
-        const GVec<VPL> xr = gload<VPL>(a.xr + ti_off);
-        GVec<VPL> g = gload<VPL>(a.gout + ti_off);
+        const GVec<VPL> xr = gload_live<VPL, LIVE>(a.xr + ti_off, lane);
+        GVec<VPL> g = gload_live<VPL, LIVE>(a.gout + ti_off, lane);
         {
-            const GVec<VPL> o = gload<VPL>(a.out + ti_off);
+            const GVec<VPL> o = gload_live<VPL, LIVE>(a.out + ti_off, lane);
 #pragma unroll
             for (int i = 0; i < VPL; ++i) g.v[i] = o.v[i] > 0.f ? g.v[i] : 0.f;     // relu'
         }
         const float* st = a.stats + ((size_t)ti * a.heads + head) * 4;
-        const float m = st[0], inv = st[1], S = st[2];
+        float m = 0.f, inv = 0.f, S = 0.f;                                         // (an idle lane belongs to no head: alpha = 0)
+        if (LIVE == 64 || lane < LIVE) m = st[0], inv = st[1], S = st[2];
         const float alpha = expf(edge_score<VPL, KIND>(a, xr, xl, att) - m) * inv;  // the targets kernel's expression
         float d = 0.f;
 #pragma unroll
@@ -310,8 +331,8 @@ __global__ __launch_bounds__(256) void gat_backward_sources_kernel(GradArgs a) {
             }
         }
     }
-    gstore<VPL>(a.dxl + me, acc_l);
-    if constexpr (KIND == MEL_CONV_TRANSFORMER) gstore<VPL>(a.dxv + me, acc_v);
+    gstore_live<VPL, LIVE>(a.dxl + me, acc_l, lane);
+    if constexpr (KIND == MEL_CONV_TRANSFORMER) gstore_live<VPL, LIVE>(a.dxv + me, acc_v, lane);
 }
 
 // ---- global pool over the graph of (x * dm): hl_dgn.py:105-108 -------------------------------------------
@@ -357,28 +378,30 @@ static mel_status check_gat(const float* xl, const float* xr, const uint64_t* ad
                             int kind, const float* att, const float* xv) {
     if (!xl || !xr || !adj) return fail(MEL_ERR_INVALID_ARG, "gat: null pointer");
     if (bs < 1 || n < 1 || n > MEL_MAX_NODES || bs * n > (1ll << 28)) return fail(MEL_ERR_INVALID_ARG, "gat: bs=%ld n=%d", (long)bs, n);
-    const int hc = heads * channels;
-    if (hc != 128 && hc != 256 && hc != 512 && hc != 1024)
-        return fail(MEL_ERR_UNSUPPORTED, "gat: heads*channels = %d not in {128,256,512,1024}", hc);
-    const int vpl = hc / 64;
-    if (channels % vpl != 0 || ((channels / vpl) & (channels / vpl - 1)))
-        return fail(MEL_ERR_UNSUPPORTED, "gat: channels per head (%d) must be a power-of-two multiple of %d", channels, vpl);
+    if (const HeadLanes hl = head_lanes(heads, channels); !hl.ok())
+        return fail(MEL_ERR_UNSUPPORTED, "gat: %d heads of %d channels: %s", heads, channels, hl.why);
     if (kind == MEL_CONV_GATV2 && !att) return fail(MEL_ERR_INVALID_ARG, "gat: att is null");
     if (kind == MEL_CONV_TRANSFORMER && !xv) return fail(MEL_ERR_INVALID_ARG, "gat: values are null");
     if (kind != MEL_CONV_GATV2 && kind != MEL_CONV_TRANSFORMER) return fail(MEL_ERR_INVALID_ARG, "gat: kind %d", kind);
     return MEL_OK;
 }
 
-#define MEL_GRAD_DISPATCH(KERNEL, grid)                                                                      \
-    switch (hc / 64) {                                                                                        \
-        case 2: if (kind == MEL_CONV_GATV2) MEL_LAUNCH((KERNEL<2, MEL_CONV_GATV2>), dim3(grid), dim3(256), 0, s, a);   \
-                else MEL_LAUNCH((KERNEL<2, MEL_CONV_TRANSFORMER>), dim3(grid), dim3(256), 0, s, a); break;            \
-        case 4: if (kind == MEL_CONV_GATV2) MEL_LAUNCH((KERNEL<4, MEL_CONV_GATV2>), dim3(grid), dim3(256), 0, s, a);   \
-                else MEL_LAUNCH((KERNEL<4, MEL_CONV_TRANSFORMER>), dim3(grid), dim3(256), 0, s, a); break;            \
-        case 8: if (kind == MEL_CONV_GATV2) MEL_LAUNCH((KERNEL<8, MEL_CONV_GATV2>), dim3(grid), dim3(256), 0, s, a);   \
-                else MEL_LAUNCH((KERNEL<8, MEL_CONV_TRANSFORMER>), dim3(grid), dim3(256), 0, s, a); break;            \
-        default: if (kind == MEL_CONV_GATV2) MEL_LAUNCH((KERNEL<16, MEL_CONV_GATV2>), dim3(grid), dim3(256), 0, s, a); \
-                 else MEL_LAUNCH((KERNEL<16, MEL_CONV_TRANSFORMER>), dim3(grid), dim3(256), 0, s, a); break;          \
+// the kernel for (channels per lane, conv kind, live lanes) of `hl` / `kind`: full wavefronts of 2 .. 16 channels per lane, and
+// the two 48-lane shapes head_lanes admits
+#define MEL_GRAD_LAUNCH(KERNEL, V, LIVE, grid)                                                                        \
+    do {                                                                                                              \
+        if (kind == MEL_CONV_GATV2) MEL_LAUNCH((KERNEL<V, MEL_CONV_GATV2, LIVE>), dim3(grid), dim3(256), 0, s, a);     \
+        else MEL_LAUNCH((KERNEL<V, MEL_CONV_TRANSFORMER, LIVE>), dim3(grid), dim3(256), 0, s, a);                     \
+    } while (0)
+#define MEL_GRAD_DISPATCH(KERNEL, grid)                                                  \
+    if (hl.live == 48) {                                                                 \
+        if (hl.vpl == 8) MEL_GRAD_LAUNCH(KERNEL, 8, 48, grid);                           \
+        else MEL_GRAD_LAUNCH(KERNEL, 16, 48, grid);                                      \
+    } else switch (hl.vpl) {                                                             \
+        case 2: MEL_GRAD_LAUNCH(KERNEL, 2, 64, grid); break;                             \
+        case 4: MEL_GRAD_LAUNCH(KERNEL, 4, 64, grid); break;                             \
+        case 8: MEL_GRAD_LAUNCH(KERNEL, 8, 64, grid); break;                             \
+        default: MEL_GRAD_LAUNCH(KERNEL, 16, 64, grid); break;                           \
     }
 
 }  // namespace mel
@@ -498,10 +521,10 @@ mel_status mel_gat_forward(const float* xl, const float* xv, const float* xr, co
     if (mel_status st = check_gat(xl, xr, adj, bs, n, heads, channels, kind, att, xv)) return st;
     if (!out) return fail(MEL_ERR_INVALID_ARG, "gat: out is null");
     clear_stale_error();
-    const int hc = heads * channels;
     GradArgs a{};
     a.xl = xl, a.xv = (kind == MEL_CONV_GATV2) ? xl : xv, a.xr = xr, a.att = att, a.bias = bias, a.adj = adj;
-    a.rows = (int)(bs * n), a.n = n, a.nw = set_words(n), a.lanes_per_head = channels / (hc / 64), a.kind = kind;
+    const HeadLanes hl = head_lanes(heads, channels);
+    a.rows = (int)(bs * n), a.n = n, a.nw = set_words(n), a.lanes_per_head = hl.lanes_per_head, a.kind = kind;
     a.scale = 1.0f / sqrtf((float)channels), a.out = out;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = (a.rows + 3) / 4;
@@ -520,7 +543,8 @@ mel_status mel_gat_backward(const float* xl, const float* xv, const float* xr, c
     const int hc = heads * channels;
     GradArgs a{};
     a.xl = xl, a.xv = (kind == MEL_CONV_GATV2) ? xl : xv, a.xr = xr, a.att = att, a.adj = adj;
-    a.rows = (int)(bs * n), a.n = n, a.nw = set_words(n), a.lanes_per_head = channels / (hc / 64), a.kind = kind;
+    const HeadLanes hl = head_lanes(heads, channels);
+    a.rows = (int)(bs * n), a.n = n, a.nw = set_words(n), a.lanes_per_head = hl.lanes_per_head, a.kind = kind;
     a.scale = 1.0f / sqrtf((float)channels);
     a.out = const_cast<float*>(out), a.gout = grad_out, a.dxl = dxl, a.dxv = dxv, a.dxr = dxr, a.datt = datt, a.dbias = dbias;
     a.stats = stats, a.heads = heads;

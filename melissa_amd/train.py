@@ -27,17 +27,62 @@ MODELS = ("l_dgn", "hl_dgn", "dgn_r", "n_dgn_r", "l_n_dgn_r", "hl_n_dgn_r")     
 N_DGN_NETWORK = {"n_dgn_r": "dgn_r", "l_n_dgn_r": "l_dgn", "hl_n_dgn_r": "hl_dgn"}
 
 
-def build_network(name: str, n_nodes: int, device, hidden=128, heads=4):
+AGGREGATORS = ("max", "mean", "add")                           # hl_dgn.py:56-60
+
+
+def check_network_args(name: str, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128),
+                       dueling_v_hidden_sizes=(128, 128), aggregator_function="max", feature_dtype=None) -> None:
+    """ValueError, with the reason, for a network shape the HIP path does not run (:func:`melissa_amd.shapes.hip_shape_supported`
+    and the dueling heads' rule of ``validate()``, csrc/fwd.hip) - before anything is built, not at the first forward.  No torch."""
+    from .shapes import MAX_HEAD_LAYERS, require_hip_shape
+    require_hip_shape(hidden_emb, num_heads)
+    q, v = list(dueling_q_hidden_sizes), list(dueling_v_hidden_sizes)
+    for flag, sizes in (("dueling_q_hidden_sizes", q), ("dueling_v_hidden_sizes", v)):
+        if any(int(x) < 64 or int(x) % 64 for x in sizes):
+            raise ValueError(f"{flag}={sizes}: every hidden layer of a dueling head must be a multiple of 64 wide")
+    if len(q) != len(v) or len(q) + 1 > MAX_HEAD_LAYERS:
+        raise ValueError(f"dueling_q_hidden_sizes={q} and dueling_v_hidden_sizes={v}: the Q and V heads must have the same depth, "
+                         f"at most {MAX_HEAD_LAYERS - 1} hidden layers")
+    if feature_dtype == "bf16" and not q:
+        # (the bf16 feature path's last head layer reads fp32 rows that only a hidden layer writes)
+        raise ValueError("feature dtype bf16 needs at least one hidden layer in the dueling heads: "
+                         "dueling_q_hidden_sizes / dueling_v_hidden_sizes are empty")
+    if aggregator_function not in AGGREGATORS:
+        raise ValueError(f"aggregator_function={aggregator_function!r}: one of {AGGREGATORS}")
+    if aggregator_function != "max" and N_DGN_NETWORK.get(name, name) != "hl_dgn":
+        raise ValueError(f"aggregator_function={aggregator_function!r} is for the HL-DGN models (hl_dgn, hl_n_dgn_r): "
+                         f"{name} has no graph pool")
+
+
+def build_network(name: str, n_nodes: int, device, hidden=128, heads=4, dueling_q_hidden_sizes=(128, 128),
+                  dueling_v_hidden_sizes=(128, 128), aggregator="max"):
+    """The reference's network of a model name at its ``--hidden-emb`` / ``--num-heads`` / ``--dueling-*-hidden-sizes`` /
+    ``--aggregator-function`` (common.py:29-30,41-43; the defaults are the reference's)."""
     from .networks import DGNRNetwork, HLDGNNetwork, LDGNNetwork
-    duel = ({"hidden_sizes": [128, 128]}, {"hidden_sizes": [128, 128]})          # common.py:41-42
+    duel = ({"hidden_sizes": [int(x) for x in dueling_q_hidden_sizes]},
+            {"hidden_sizes": [int(x) for x in dueling_v_hidden_sizes]})          # common.py:41-42
     name = N_DGN_NETWORK.get(name, name)
     if name == "l_dgn":
         return LDGNNetwork(5, hidden, 2, heads, n_nodes, dueling_param=duel, device=device)
     if name == "hl_dgn":
-        return HLDGNNetwork(5, hidden, 2, heads, n_nodes, aggregator="max", dueling_param=duel, device=device)
+        return HLDGNNetwork(5, hidden, 2, heads, n_nodes, aggregator=aggregator, dueling_param=duel, device=device)
     if name == "dgn_r":
         return DGNRNetwork(5, hidden, 2, heads, n_nodes, dueling_param=duel, device=device)
     raise ValueError(name)
+
+
+def load_policy_weights(policy, path, device) -> None:
+    """``policy.load_state_dict`` of a saved policy (keys ``model.*`` / ``model_old.*``).  A checkpoint trained at another
+    ``--hidden-emb`` / ``--num-heads`` / dueling shape fails HERE, naming the first mismatching key and both shapes."""
+    import torch
+    sd = torch.load(path, map_location=device, weights_only=True)
+    own = policy.state_dict()
+    for key, value in sd.items():
+        if key in own and tuple(own[key].shape) != tuple(value.shape):
+            raise ValueError(f"{path} was trained at another network shape: {key} is {tuple(value.shape)} in the checkpoint and "
+                             f"{tuple(own[key].shape)} in the network built here (--hidden-emb / --num-heads / "
+                             f"--dueling-q-hidden-sizes / --dueling-v-hidden-sizes must be the training run's)")
+    policy.load_state_dict(sd)
 
 
 def policy_and_learner(name: str):
@@ -287,7 +332,9 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           probe=None, graphs=16, ring=16, capture_updates=None, prio_buffer=False, alpha=0.6, beta=0.4,
           heuristic=None, scripted_agents_ratio=0.0, epoch=None, step_per_epoch=100000, eps_train=1.0, eps_train_final=0.05,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
-          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes", graph_pool=None):
+          update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes", graph_pool=None,
+          hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
+          aggregator_function="max"):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -325,7 +372,12 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     reports their means (``train_info_rows``, ``train_<key>``: per epoch record, or over the whole run in the fixed-updates
     mode; each rank pools its own envs, rank 0 reports).  An epoch record is written before that epoch's evaluation and its
     pool is read and emptied there, so it holds the training rounds since the previous record and never an evaluation's (those
-    run on envs of their own); the record of epoch 0 holds the pre-fill rounds.  "episodes" (the default) pools nothing."""
+    run on envs of their own); the record of epoch 0 holds the pre-fill rounds.  "episodes" (the default) pools nothing.
+    ``hidden_emb`` / ``num_heads`` / ``dueling_q_hidden_sizes`` / ``dueling_v_hidden_sizes`` / ``aggregator_function``: the
+    reference's network flags (common.py:29-30,41-43) with its defaults; a shape the HIP path does not run is a ValueError with
+    the reason before anything is built (:func:`check_network_args`); a run at another shape than the default 128 x 4 records
+    ``hidden_emb`` and ``num_heads`` in its result."""
+    check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function)
     if collect_stats not in ("episodes", "steps"):
         raise ValueError(f"collect_stats={collect_stats!r}: 'episodes' or 'steps'")
     if int(test_envs) < 1:
@@ -350,14 +402,16 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     device = torch.device("cuda", local_rank if backend != "gloo" else 0)
     torch.cuda.set_device(device)
     torch.manual_seed(seed)                                    # same init everywhere, then broadcast anyway
-    net = build_network(model, n_nodes, device)
+    net = build_network(model, n_nodes, device, hidden=hidden_emb, heads=num_heads,
+                        dueling_q_hidden_sizes=dueling_q_hidden_sizes, dueling_v_hidden_sizes=dueling_v_hidden_sizes,
+                        aggregator=aggregator_function)
     parallel.broadcast_parameters(net, src=0)
     policy_cls, learner_cls, neighbours = policy_and_learner(model)
     policy = policy_cls(net, torch.optim.Adam(net.parameters(), lr=lr), discount_factor=gamma,
                         estimation_step=n_step, target_update_freq=target_update_freq)
     if resume_path is not None:
         # --resume-path (l_dgn.py:311 load_policy): the weights of a saved policy, model.* and model_old.*, nothing else
-        policy.load_state_dict(torch.load(resume_path, map_location=device, weights_only=True))
+        load_policy_weights(policy, resume_path, device)
         parallel.broadcast_parameters(net, src=0)
     checksum_start = _param_checksum(net) if epoch is not None else None      # (what the first update starts from)
     if graph_pool is not None:
@@ -478,6 +532,9 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                warmup_updates=warmup_updates, heuristic=heuristic, scripted_agents_ratio=float(scripted_agents_ratio),
                episode_supply=loop.supply.describe())
     out.update(extra)
+    if (int(hidden_emb), int(num_heads)) != (128, 4):
+        # a run at another shape than the reference's default records it (the keys of a default run stay what they were)
+        out.update(hidden_emb=int(hidden_emb), num_heads=int(num_heads))
     if pooled is not None and epoch is None:
         out.update(pooled())
     # replicas must be identical after averaged-gradient steps
@@ -541,6 +598,13 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--logdir", type=str, default="log")
     ap.add_argument("--model-name", type=str, default=default_model_name())
     ap.add_argument("--resume-path", type=str, default=None)
+    # the reference's network flags, names and defaults (common.py:29-30,41-43)
+    ap.add_argument("--hidden-emb", type=int, default=128, help="encoder width and channels per attention head")
+    ap.add_argument("--num-heads", type=int, default=4, help="attention heads (a power of two, or 6)")
+    ap.add_argument("--dueling-q-hidden-sizes", type=int, nargs="*", default=[128, 128])
+    ap.add_argument("--dueling-v-hidden-sizes", type=int, nargs="*", default=[128, 128])
+    ap.add_argument("--aggregator-function", type=str, default="max", choices=list(AGGREGATORS),
+                    help="graph pool of the HL-DGN models")
     ap.add_argument("--seed", type=int, default=9)
     ap.add_argument("--lr", type=float, default=0.001)
     ap.add_argument("--gamma", type=float, default=0.99)
@@ -560,13 +624,21 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 eps_test=a.eps_test, test_num=a.test_num, logdir=a.logdir, model_name=a.model_name, resume_path=a.resume_path,
                 seed=a.seed, lr=a.lr, gamma=a.gamma, n_step=a.n_step, target_update_freq=a.target_update_freq,
                 update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size,
-                test_envs=a.test_envs, collect_stats=a.collect_stats, graph_pool=a.graph_pool)
+                test_envs=a.test_envs, collect_stats=a.collect_stats, graph_pool=a.graph_pool,
+                hidden_emb=a.hidden_emb, num_heads=a.num_heads, dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
+                dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
-    """The command line, with what argparse alone cannot say: ``--update-per-step`` needs ``--epoch``."""
+    """The command line, with what argparse alone cannot say: ``--update-per-step`` needs ``--epoch``, and the network flags
+    must name a shape the HIP path runs (an error here, with the reason, not at the first forward)."""
     ap = arg_parser()
     a = ap.parse_args(argv)
+    try:
+        check_network_args(a.model, a.hidden_emb, a.num_heads, a.dueling_q_hidden_sizes, a.dueling_v_hidden_sizes,
+                           a.aggregator_function)
+    except ValueError as e:
+        ap.error(str(e))
     if a.update_per_step is not None and a.epoch is None:
         ap.error("--update-per-step paces the updates of the epoch mode: it needs --epoch")
     import sys
@@ -576,11 +648,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     return a
 
 
-def main():
-    a = parse_args()
+def main(argv=None):
+    a = parse_args(argv)
     import sys
     from . import launch
-    rc = launch.maybe_spawn("-m", ["melissa_amd.train", *sys.argv[1:]], a.gpus, check_devices=a.backend != "gloo")
+    given = sys.argv[1:] if argv is None else list(argv)
+    rc = launch.maybe_spawn("-m", ["melissa_amd.train", *given], a.gpus, check_devices=a.backend != "gloo")
     if rc is not None:
         raise SystemExit(rc)
     train(**train_kwargs(a))

@@ -26,24 +26,30 @@ import torch
 from .collect import Collector, evaluate_spread
 from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
-from .train import N_DGN_NETWORK, build_network
+from .train import AGGREGATORS, N_DGN_NETWORK, build_network, check_network_args, load_policy_weights
 
 
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
           dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
-          graphs=16):
+          graphs=16, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
+          aggregator_function="max"):
     """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
     random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
     ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
     statistic, pooled on the device; ``n_info_rows`` steps) instead of over the episodes' final rows.  Not with ``spread``:
-    the envs that finish their share early keep playing, and those surplus episodes would enter the pool."""
+    the envs that finish their share early keep playing, and those surplus episodes would enter the pool.
+    ``hidden_emb`` ... ``aggregator_function``: the network flags of :func:`melissa_amd.train.train`; ``load`` of a checkpoint
+    trained at another shape is a ValueError naming the mismatching key and both shapes."""
+    check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function,
+                       feature_dtype=feature_dtype)
     if spread and collect_stats != "episodes":
         raise ValueError("collect_stats='steps' is not offered with spread: surplus episodes would enter the pool")
     torch.manual_seed(seed)
-    net = build_network(model, n_nodes, device)
+    net = build_network(model, n_nodes, device, hidden=hidden_emb, heads=num_heads, dueling_q_hidden_sizes=dueling_q_hidden_sizes,
+                        dueling_v_hidden_sizes=dueling_v_hidden_sizes, aggregator=aggregator_function)
     policy = DQNPolicy(net, target_update_freq=1)
     if load:
-        policy.load_state_dict(torch.load(load, map_location=device, weights_only=True))
+        load_policy_weights(policy, load, device)
     net.eval()
     net.set_feature_dtype(feature_dtype)
     if isinstance(graph_pool, str):
@@ -89,21 +95,40 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--collect-stats", choices=["episodes", "steps"], default="episodes",
                     help="steps: the logger_stats means are taken over every env step played (the reference's statistic), not "
                          "over the episodes' final rows; not with --spread")
+    # the reference's network flags, names and defaults (common.py:29-30,41-43): those of the run that trained --load
+    ap.add_argument("--hidden-emb", type=int, default=128, help="encoder width and channels per attention head")
+    ap.add_argument("--num-heads", type=int, default=4, help="attention heads (a power of two, or 6)")
+    ap.add_argument("--dueling-q-hidden-sizes", type=int, nargs="*", default=[128, 128])
+    ap.add_argument("--dueling-v-hidden-sizes", type=int, nargs="*", default=[128, 128])
+    ap.add_argument("--aggregator-function", type=str, default="max", choices=list(AGGREGATORS),
+                    help="graph pool of the HL-DGN models")
     return ap
 
 
-def main(argv=None):
+def parse_args(argv=None) -> argparse.Namespace:
     ap = arg_parser()
     a = ap.parse_args(argv)
+    try:
+        check_network_args(a.model, a.hidden_emb, a.num_heads, a.dueling_q_hidden_sizes, a.dueling_v_hidden_sizes,
+                           a.aggregator_function, feature_dtype=a.dtype)
+    except ValueError as e:
+        ap.error(str(e))
     if a.spread and a.collect_stats != "episodes":
         ap.error("--collect-stats steps is not offered with --spread (surplus episodes would enter the pool)")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     import sys
     given = sys.argv[1:] if argv is None else argv
     if a.graph_pool is not None and any(x == "--graphs" or x.startswith("--graphs=") for x in given):
         print(f"--graph-pool {a.graph_pool} is the graph pool: --graphs {a.graphs} is ignored", file=sys.stderr)
     print(json.dumps(watch(a.model, a.nodes, a.envs, a.episodes, a.load, feature_dtype=a.dtype, heuristic=a.heuristic,
                            scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread, collect_stats=a.collect_stats,
-                           graph_pool=a.graph_pool, graphs=a.graphs)))
+                           graph_pool=a.graph_pool, graphs=a.graphs, hidden_emb=a.hidden_emb, num_heads=a.num_heads,
+                           dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
+                           dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function)))
 
 
 if __name__ == "__main__":
