@@ -75,6 +75,7 @@ __global__ __launch_bounds__(256) void encoder_layer0_kernel(GemmArgs g, float* 
 // The encoder launch of problem g (an ENC-mode problem: obs / nid or feat_domain, enc_w, enc_b): the GEMM's fused producer
 // where the encoder fits it, else layer 0 into `scratch` (g.M rows of g.K values) and a PLAIN GEMM on those rows.
 static mel_status launch_encoder(GemmArgs g, float* scratch, hipStream_t s, const char* what, long m_hint = -1) {
+    StageScope t(MEL_STAGE_ENCODER, s);
     if (g.K <= ENC_FUSED_MAX_K) return launch_gemm(g, GEMM_MODE_ENC, s, what, m_hint);
     if (!scratch) return fail(MEL_ERR_WORKSPACE, "%s: no scratch for the rows of an encoder %d wide", what, g.K);
     if (g.M <= 0) return MEL_OK;
@@ -209,22 +210,39 @@ static int head_hidden_width(const mel_mlp& m) {
     return w;
 }
 
+// What the functions below derive from the weights (validate() keeps its own arithmetic: it runs before these can be trusted)
+struct NetShape {
+    int K0, hidden; // widths of encoder layer 0 and of the encoder rows
+    int hc;         // heads * channels: a conv's output row
+    int srcw;       // a conv's source-side row: HL-DGN's lin_l | lin_r and a transformer conv's key | value lie side by side
+    int latent;     // head input
+    int bf, sp;     // bf16 feature path, MEL_PREC_F32_SPLIT
+    bool tconv, hl;
+};
+static NetShape shape_of(const mel_weights* w) {
+    NetShape z;
+    z.K0 = w->encoder.layer[0].out_dim, z.hidden = w->encoder.layer[1].out_dim, z.hc = w->conv1.heads * w->conv1.channels;
+    z.tconv = w->conv1.kind == MEL_CONV_TRANSFORMER, z.hl = w->model == MEL_MODEL_HLDGN;
+    z.srcw = z.hl || z.tconv ? 2 * z.hc : z.hc, z.latent = w->q_head.layer[0].in_dim;
+    z.bf = w->precision == MEL_PREC_BF16, z.sp = w->precision == MEL_PREC_F32_SPLIT;
+    return z;
+}
+
 static FwdLayout carve(const mel_weights* w, const Dims& d, void* ws) {
     FwdLayout L{};
     Carver c(ws);
-    const int hidden = w->encoder.layer[1].out_dim;
-    const int hc = w->conv1.heads * w->conv1.channels;
+    const NetShape z = shape_of(w);
+    const int hidden = z.hidden, hc = z.hc, srcw = z.srcw, latent = z.latent;
     const size_t M = (size_t)d.bs * d.n;
     const size_t R = (size_t)d.rows_cap;
     const size_t SW = (size_t)set_words(d.n);          // words per node set
     L.plan.adj = c.take<uint64_t>(M * SW);
     L.plan.live = c.take<uint64_t>(d.bs * SW);
-    const int latent = w->q_head.layer[0].in_dim;
     // node-feature table mode: the encoder / conv1-projection buffers must also hold the N * 40 table rows
     const size_t T = (size_t)d.n * FEATURE_TUPLES_PER_DEGREE;
     const size_t rows2 = (size_t)d.u2_cap > T ? (size_t)d.u2_cap : T, rows1 = (size_t)d.u1_cap > T ? (size_t)d.u1_cap : T;
     const size_t rowsM = M > T ? M : T;
-    if (w->model != MEL_MODEL_HLDGN) {
+    if (!z.hl) {
         L.plan.u1 = c.take<uint64_t>(d.bs * SW);
         L.plan.u2 = c.take<uint64_t>(d.bs * SW);
         L.plan.cnt = c.take<int32_t>(3 * d.bs);
@@ -241,7 +259,6 @@ static FwdLayout carve(const mel_weights* w, const Dims& d, void* ws) {
         L.plan.arow_g = c.take<int32_t>(R);
         L.plan.dm_g = c.take<float>(R);
         L.h0 = c.take<float>(rows2 * hidden);
-        const int srcw = (w->conv1.kind == MEL_CONV_TRANSFORMER) ? 2 * hc : hc;     // key | value side by side
         L.xl1 = c.take<float>(rows2 * srcw);
         L.xr1 = c.take<float>(rows1 * hc);
         // (fp32 rows, or - conv2 on gemm_planes_kernel - three bf16 planes: 6 bytes per value)
@@ -250,7 +267,7 @@ static FwdLayout carve(const mel_weights* w, const Dims& d, void* ws) {
         L.xr2 = c.take<float>(R * hc);
     } else {
         L.h0 = c.take<float>(rowsM * hidden);
-        L.xl1 = c.take<float>(rowsM * 2 * hc);
+        L.xl1 = c.take<float>(rowsM * srcw);
     }
     L.plan.fid = c.take<int32_t>(M);
     L.plan.fbad = c.take<int32_t>(d.bs);
@@ -266,7 +283,7 @@ static FwdLayout carve(const mel_weights* w, const Dims& d, void* ws) {
     L.wb = c.take<uint16_t>(L.wb_elems ? L.wb_elems : 8);
     // (taken last, and only for a wide encoder: every other shape keeps its layout)
     L.enc0 = encoder_fuses(w) ? nullptr
-                              : c.take<float>((w->model != MEL_MODEL_HLDGN ? rows2 : rowsM) * (size_t)w->encoder.layer[0].out_dim);
+                              : c.take<float>((z.hl ? rowsM : rows2) * (size_t)z.K0);
     L.bytes = c.off;
     L.rows_cap = R;
     return L;
@@ -419,8 +436,7 @@ static mel_status run_heads(const mel_weights* w, const ProjWeights& pw, const F
                             const int32_t* rows_dev, long rows_hint, float* logits, hipStream_t s,
                             const mel_select* select = nullptr) {
     const int nl = w->q_head.n_layers;
-    const int bf = w->precision == MEL_PREC_BF16;
-    const int sp = w->precision == MEL_PREC_F32_SPLIT;
+    const int bf = shape_of(w).bf, sp = shape_of(w).sp;
     const float* in_q = L.xcat;
     const float* in_v = L.xcat;
     int ld_q = w->q_head.layer[0].in_dim, ld_v = ld_q;
@@ -525,14 +541,12 @@ struct FeatureTables {
 static size_t table_elem_bytes(const mel_weights* w) { return w->precision == MEL_PREC_BF16 ? 2 : 4; }
 static FeatureTables carve_tables(const mel_weights* w, int n, void* buf, size_t* bytes) {
     const size_t T = (size_t)n * FEATURE_TUPLES_PER_DEGREE, es = table_elem_bytes(w);
-    const int hidden = w->encoder.layer[1].out_dim, hc = w->conv1.heads * w->conv1.channels;
-    const bool hl = w->model == MEL_MODEL_HLDGN;
-    const int srcw = hl ? 2 * hc : (w->conv1.kind == MEL_CONV_TRANSFORMER ? 2 * hc : hc);
+    const NetShape z = shape_of(w);
     Carver c(buf);
     FeatureTables t;
-    t.h0 = reinterpret_cast<float*>(c.take<char>(T * hidden * es));
-    t.xl = reinterpret_cast<float*>(c.take<char>(T * srcw * es));
-    t.xr = hl ? nullptr : reinterpret_cast<float*>(c.take<char>(T * hc * es));
+    t.h0 = reinterpret_cast<float*>(c.take<char>(T * z.hidden * es));
+    t.xl = reinterpret_cast<float*>(c.take<char>(T * z.srcw * es));
+    t.xr = z.hl ? nullptr : reinterpret_cast<float*>(c.take<char>(T * z.hc * es));
     if (bytes) *bytes = c.off;
     return t;
 }
@@ -540,14 +554,14 @@ static FeatureTables carve_tables(const mel_weights* w, int n, void* buf, size_t
 // MEL_PREC_F32_AUTO, whose table launches are far too small for the split kernels.  Everything else (the bf16 feature path,
 // MEL_PREC_F32_SPLIT, DGN-R's three source-side matrices, HL-DGN) keeps the two-launch form.
 static bool table_fuses(const mel_weights* w) {
-    const int hc = w->conv1.heads * w->conv1.channels, K0 = w->encoder.layer[0].out_dim;
-    return w->model == MEL_MODEL_LDGN && w->conv1.kind != MEL_CONV_TRANSFORMER &&
+    const NetShape z = shape_of(w);
+    return w->model == MEL_MODEL_LDGN && !z.tconv &&
            (w->precision == MEL_PREC_F32 || w->precision == MEL_PREC_F32_AUTO) && w->in_dim == 5 && w->encoder.n_layers == 2 &&
-           K0 == TBL_HIDDEN && w->encoder.layer[1].out_dim == TBL_HIDDEN &&
-           w->conv1.lin_l.in_dim == TBL_HIDDEN && hc % 32 == 0 && (2 * hc) % TBL_BN == 0;
+           z.K0 == TBL_HIDDEN && z.hidden == TBL_HIDDEN &&
+           w->conv1.lin_l.in_dim == TBL_HIDDEN && z.hc % 32 == 0 && (2 * z.hc) % TBL_BN == 0;
 }
 static TableArgs fused_table_args(const mel_weights* w, const ProjWeights& pw, int n, const FeatureTables& t) {
-    const int hc = w->conv1.heads * w->conv1.channels;
+    const int hc = shape_of(w).hc;
     TableArgs a;
     a.T = n * FEATURE_TUPLES_PER_DEGREE, a.in_dim = w->in_dim;
     a.enc_w = w->encoder.layer[0].weight, a.enc_b = w->encoder.layer[0].bias;
@@ -558,47 +572,94 @@ static TableArgs fused_table_args(const mel_weights* w, const ProjWeights& pw, i
     return a;
 }
 
+// The GEMM problems of the encoder and of conv1, each described ONCE: everything the weights and the precision decide.  The
+// caller adds the rows (M, M_dev) and the gathers (nid, arow).
+// The encoder, relu(W1 relu(W0 x + b0) + b1) into rows of Y (l_dgn.py:117-118): what its two problems share
+static GemmArgs encoder_problem(const mel_weights* w, const NetShape& z, const float* W1, float* Y) {
+    GemmArgs g;
+    g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
+    g.W = W1, g.bias = w->encoder.layer[1].bias, g.split = split_k(z.sp, z.K0);
+    g.Y = Y, g.ldy = z.hidden, g.N = z.hidden, g.K = z.K0, g.relu = 1;
+    return g;
+}
+// ... on observation rows: L-DGN's U2 rows (the caller sets nid) and every node of HL-DGN
+static GemmArgs encoder_on_rows(const mel_weights* w, const ProjWeights& pw, const NetShape& z, const float* obs, int obs_stride,
+                                int n, float* Y) {
+    GemmArgs g = encoder_problem(w, z, pw.enc1, Y);
+    g.obs = obs, g.obs_width = obs_stride, g.n_nodes = n, g.node_cols = w->in_dim + 3, g.bf16 = z.bf;
+    return g;
+}
+// ... on the n * 40 feature tuples of the node-feature table.  bf16 feature path: the exact-fp32 tile on the fp32 weights, its
+// rows stored as bf16, as a launch of its own and beside the plan - so prepared and per-call tables are identical
+static GemmArgs encoder_on_tuples(const mel_weights* w, const ProjWeights& pw, const NetShape& z, int n, float* Y) {
+    GemmArgs g = encoder_problem(w, z, z.bf ? w->encoder.layer[1].weight : pw.enc1, Y);
+    g.feat_domain = 1, g.y_bf16 = z.bf, g.M = n * FEATURE_TUPLES_PER_DEGREE;
+    return g;
+}
+// ... as the 64 x 64 tiles of gemm_f32_kernel, one workgroup each: the first enc.grid workgroups of plan_enc_kernel / fid_enc_kernel
+static mel_status plan_encoder_beside_plan(const mel_weights* w, const ProjWeights& pw, const NetShape& z, int n, float* Y, GemmPlan& enc) {
+    const GemmArgs g = encoder_on_tuples(w, pw, z, n, Y);
+    GemmRequest rq;
+    rq.mode = GEMM_MODE_ENC, rq.force_tile = MEL_TILE_64;
+    enc = plan_gemm(&g, nullptr, 1, rq);
+    return enc.status ? fail(enc.status, "encoder (feature tuples): %s", enc.why) : MEL_OK;
+}
+// conv1 of L-DGN / DGN-R on rows of t.h0: g[0] = lin_l for the sources (DGN-R: key | value in one problem, the weights split
+// along n) into t.xl, g[1] = lin_r for the targets into t.xr
+static void conv1_pair(const mel_weights* w, const ProjWeights& pw, const NetShape& z, const FeatureTables& t, GemmArgs g[2]) {
+    g[0].bf16 = g[1].bf16 = z.bf, g[0].split = g[1].split = split_k(z.sp, z.hidden);
+    g[0].A = t.h0, g[0].lda = z.hidden, g[0].W = pw.c1l, g[0].bias = w->conv1.lin_l.bias;
+    g[0].Y = t.xl, g[0].ldy = z.srcw, g[0].N = z.srcw, g[0].K = z.hidden;
+    if (z.tconv) g[0].W_hi = pw.c1v, g[0].bias_hi = w->conv1.lin_v.bias, g[0].split_n = z.hc;
+    g[1].A = t.h0, g[1].lda = z.hidden, g[1].W = pw.c1r, g[1].bias = w->conv1.lin_r.bias;
+    g[1].Y = t.xr, g[1].ldy = z.hc, g[1].N = z.hc, g[1].K = z.hidden;
+}
+// conv1 of HL-DGN: x_l | x_r of every row of t.h0 in one GEMM (weights split along n) into t.xl
+static GemmArgs conv1_hl(const mel_weights* w, const ProjWeights& pw, const NetShape& z, const FeatureTables& t) {
+    GemmArgs g;
+    g.A = t.h0, g.lda = z.hidden, g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = z.bf, g.split = split_k(z.sp, z.hidden);
+    g.bias = w->conv1.lin_l.bias, g.bias_hi = w->conv1.lin_r.bias, g.split_n = z.hc;
+    g.Y = t.xl, g.ldy = z.srcw, g.N = z.srcw, g.K = z.hidden;
+    return g;
+}
+
+// A forward of env observations (integer features) takes the node-feature table (plan_masks.hpp) when it expects `rows` rows
+// in its lists, much more than the n * 40 tuples ...
+static bool takes_table(const mel_weights* w, int n, long rows) {
+    return (w->flags & MEL_FWD_INTEGER_FEATURES) && w->in_dim == 5 && rows >= 2L * n * FEATURE_TUPLES_PER_DEGREE;
+}
+// ... the one the caller prepared for these weights and this n (mel_prepare_feature_tables) ...
+static bool tables_prepared(const mel_weights* w, int n) { return w->tables && w->tables_nodes == n; }
+// ... or its own, whose encoder rows ride in the plan launch: they and the row lists (HL-DGN: the tuple ids) are independent,
+// ONE launch runs both instead of two latency-bound ones back to back (the bf16 ENC launch of 2 000 tuples alone took 15 us)
+static bool encoder_rides_in_plan(const mel_weights* w, const NetShape& z, int n, bool table) {
+    return table && !z.sp && !tables_prepared(w, n) && encoder_fuses(w);
+}
+
 static mel_status run_feature_tables(const mel_weights* w, const ProjWeights& pw, int n, const FeatureTables& t, hipStream_t s,
                                      bool encoder_done = false, float* enc0 = nullptr) {
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
-    const int hidden = w->encoder.layer[1].out_dim, hc = w->conv1.heads * w->conv1.channels;
-    const int bf = w->precision == MEL_PREC_BF16, sp = w->precision == MEL_PREC_F32_SPLIT;
-    const bool tconv = w->conv1.kind == MEL_CONV_TRANSFORMER, hl = w->model == MEL_MODEL_HLDGN;
+    const NetShape z = shape_of(w);
     if (!encoder_done) {
-        GemmArgs g;
-        g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
-        // bf16 feature path: the table's encoder rows come from the exact-fp32 tile on the fp32 weights, stored as bf16 - the form
-        // the forward's fused launch (plan_enc_kernel / fid_enc_kernel) evaluates, so prepared and per-call tables are identical
-        if (bf) g.W = w->encoder.layer[1].weight, g.bf16 = 0, g.y_bf16 = 1;
-        g.Y = t.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-        StageScope sc(MEL_STAGE_ENCODER, s);
+        const GemmArgs g = encoder_on_tuples(w, pw, z, n, t.h0);
         // a wide encoder without scratch of the caller's (the prepared tables): its layer-0 rows pass through t.xl, which the
         // projections below write only after the encoder has read them - where they fit
         if (!enc0 && !encoder_fuses(w)) {
-            const size_t srcw = hl ? 2 * (size_t)hc : (tconv ? 2 * (size_t)hc : (size_t)hc);
-            if (srcw * table_elem_bytes(w) < (size_t)g.K * (g.bf16 ? 2 : 4))
+            if ((size_t)z.srcw * table_elem_bytes(w) < (size_t)g.K * 4)
                 return fail(MEL_ERR_UNSUPPORTED, "feature tables: an encoder %d wide needs rows of %d bytes, the table's are narrower", g.K, g.K * 4);
             enc0 = t.xl;
         }
         if (mel_status st = launch_encoder(g, enc0, s, "encoder (feature tuples)", T)) return st;
     }
     StageScope sc(MEL_STAGE_CONV1_LIN, s);
-    if (hl) {
-        GemmArgs g;
-        g.A = t.h0, g.lda = hidden, g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = split_k(sp, hidden);
-        g.bias = w->conv1.lin_l.bias, g.bias_hi = w->conv1.lin_r.bias, g.split_n = hc;
-        g.Y = t.xl, g.ldy = 2 * hc, g.M = T, g.N = 2 * hc, g.K = hidden;
+    if (z.hl) {
+        GemmArgs g = conv1_hl(w, pw, z, t);
+        g.M = T;
         return launch_gemm(g, GEMM_MODE_PLAIN, s, "conv1.lin_l|lin_r (feature tuples)");
     }
-    const int srcw = tconv ? 2 * hc : hc;
     GemmArgs g[2];
-    g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = split_k(sp, hidden);
-    g[0].A = t.h0, g[0].lda = hidden, g[0].W = pw.c1l, g[0].bias = w->conv1.lin_l.bias;
-    g[0].Y = t.xl, g[0].ldy = srcw, g[0].M = T, g[0].N = srcw, g[0].K = hidden;
-    if (tconv) g[0].W_hi = pw.c1v, g[0].bias_hi = w->conv1.lin_v.bias, g[0].split_n = hc;
-    g[1].A = t.h0, g[1].lda = hidden, g[1].W = pw.c1r, g[1].bias = w->conv1.lin_r.bias;
-    g[1].Y = t.xr, g[1].ldy = hc, g[1].M = T, g[1].N = hc, g[1].K = hidden;
+    conv1_pair(w, pw, z, t, g);
+    g[0].M = g[1].M = T;
     const long hints[2] = {T, T};
     return launch_gemm_group(g, hints, 2, s, "conv1.lin_l + lin_r (feature tuples)", 1);
 }
@@ -614,10 +675,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     const int64_t bs = d.bs;
     const int n = d.n;
     const int node_cols = w->in_dim + 3;
-    const int hidden = w->encoder.layer[1].out_dim, hc = w->conv1.heads * w->conv1.channels;
-    const int latent = hidden + 2 * hc;
-    const bool tconv = w->conv1.kind == MEL_CONV_TRANSFORMER;
-    const int srcw = tconv ? 2 * hc : hc;          // source-side projection width (key | value)
+    const NetShape z = shape_of(w);
     const int R = (int)d.rows_cap, U1 = (int)d.u1_cap, U2 = (int)d.u2_cap;
     const int32_t* nL = L.plan.offL + bs;
     const int32_t* n1 = L.plan.off1 + bs;
@@ -626,8 +684,6 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     // (N = 50): one agent per row: |U1| ~ 0.13 N, |U2| ~ 0.25 N; a whole round (about 0.1 N active agents
     // with overlapping neighbourhoods): |U1| ~ 0.21 N, |U2| ~ 0.32 N.
     const bool single = agent_mask == nullptr;
-    const int bf = w->precision == MEL_PREC_BF16;
-    const int sp = w->precision == MEL_PREC_F32_SPLIT;
     ProjWeights pw, pw_alt;
     if (mel_status st = resolve_projections(w, L, pw, pw_alt, s)) return st;
     // round-batched loop, measured on the bench workload (per env, N = 20 / 50): |L| = 3.1 / 4.7, |U1| = 5.8 / 10.4,
@@ -635,25 +691,29 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     const long hintL = single ? bs : (n < 10 ? bs : bs * (long)(36 + n) / 18);
     const long hint1 = single ? bs * (long)(n < 8 ? n : 2 + n / 8) : (n < 10 ? bs * (long)n : bs * 2L * (18 + n) / 13);
     const long hint2 = single ? bs * (long)(n < 8 ? n : 1 + n / 4) : (n < 10 ? bs * (long)n : bs * 3L * (8 + n) / 11);
-    // Node-feature table (plan_masks.hpp): worth it when the row lists are much longer than the N * 40 tuples
     const int T = n * FEATURE_TUPLES_PER_DEGREE;
-    const bool table = (w->flags & MEL_FWD_INTEGER_FEATURES) && w->in_dim == 5 && hint1 + hint2 >= 2L * T;
-    bool fused_enc = false, fused_table = false;
+    const bool table = takes_table(w, n, hint1 + hint2);
+    // (where table_fused_tile fits, the plan launch's workgroups run conv1's projections of their encoder rows too: the whole table)
+    const bool fused_enc = encoder_rides_in_plan(w, z, n, table);
+    const bool fused_table = fused_enc && table_fuses(w) && !gemm_tuning().no_fused_table;
+    // the encoder / conv1-projection rows the conv1 attention reads: the workspace's, unless the caller prepared tables
+    FeatureTables ft{L.h0, L.xl1, L.xr1};
+    if (table && tables_prepared(w, n)) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
     // conv2's projections, planned HERE: on gemm_planes_kernel (both operands as bf16 planes in blocks, gemm_split.hpp) the
     // conv1 attention stores h1 already split, as that kernel's A operand.  (h1 rows are masked by the decision-maker flag,
     // l_dgn.py:128: the conv1 attention applies it as it stores them.)
     GemmArgs c2[2];
-    c2[0].bf16 = c2[1].bf16 = bf, c2[0].split = c2[1].split = sp;
-    c2[0].A = L.h1, c2[0].lda = hc;
+    c2[0].bf16 = c2[1].bf16 = z.bf, c2[0].split = c2[1].split = z.sp;
+    c2[0].A = L.h1, c2[0].lda = z.hc;
     c2[0].W = pw.c2l, c2[0].bias = w->conv2.lin_l.bias;
-    c2[0].Y = L.xl2, c2[0].ldy = srcw, c2[0].M = U1, c2[0].M_dev = n1, c2[0].N = srcw, c2[0].K = hc;
-    if (tconv) c2[0].W_hi = pw.c2v, c2[0].bias_hi = w->conv2.lin_v.bias, c2[0].split_n = hc;
-    c2[1].A = L.h1, c2[1].lda = hc, c2[1].arow = L.plan.arow_g;
+    c2[0].Y = L.xl2, c2[0].ldy = z.srcw, c2[0].M = U1, c2[0].M_dev = n1, c2[0].N = z.srcw, c2[0].K = z.hc;
+    if (z.tconv) c2[0].W_hi = pw.c2v, c2[0].bias_hi = w->conv2.lin_v.bias, c2[0].split_n = z.hc;
+    c2[1].A = L.h1, c2[1].lda = z.hc, c2[1].arow = L.plan.arow_g;
     c2[1].W = pw.c2r, c2[1].bias = w->conv2.lin_r.bias;
-    if (pw.alt) c2[0].Ws = pw.alt->c2l, c2[0].Ws_hi = tconv ? pw.alt->c2v : nullptr, c2[1].Ws = pw.alt->c2r;
-    c2[1].Y = L.xr2, c2[1].ldy = hc, c2[1].M = R, c2[1].M_dev = nL, c2[1].N = hc, c2[1].K = hc;
+    if (pw.alt) c2[0].Ws = pw.alt->c2l, c2[0].Ws_hi = z.tconv ? pw.alt->c2v : nullptr, c2[1].Ws = pw.alt->c2r;
+    c2[1].Y = L.xr2, c2[1].ldy = z.hc, c2[1].M = R, c2[1].M_dev = nL, c2[1].N = z.hc, c2[1].K = z.hc;
     const long c2_hints[2] = {hint1, hintL};
-    const ProjWeights* planes = sp ? &pw : pw.alt;
+    const ProjWeights* planes = z.sp ? &pw : pw.alt;
     GemmRequest c2_rq;
     c2_rq.group = true;
     PlaneBlocks c2_blocks[2];
@@ -661,7 +721,7 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     //  384 or 768 wide, stay fp32 rows, so the planner is never offered the plane blocks for them)
     const HeadLanes hl1 = head_lanes(w->conv1.heads, w->conv1.channels);
     if (planes && hl1.live == 64 && hl1.vpl >= 4) {
-        c2_blocks[0] = {planes->c2l_blk, tconv ? planes->c2v_blk : nullptr}, c2_blocks[1] = {planes->c2r_blk, nullptr};
+        c2_blocks[0] = {planes->c2l_blk, z.tconv ? planes->c2v_blk : nullptr}, c2_blocks[1] = {planes->c2r_blk, nullptr};
         c2_rq.blocks = c2_blocks;
     }
     const GemmPlan conv2 = plan_gemm(c2, c2_hints, 2, c2_rq);
@@ -680,77 +740,41 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
             MEL_LAUNCH(plan_scan_kernel, dim3(1), dim3(1024), 0, s, (int)bs, L.plan);
             if (mel_status st = check_launch("plan_scan")) return st;
         }
-        // fp32 + node-feature table: the row lists and the encoder rows of the feature tuples (which depend on the weights
-        // only) are independent - ONE launch runs both (plan_enc_kernel) instead of two latency-bound ones back to back
-        // (bf16 feature path: the same fp32 tile on the fp32 encoder weights, its rows stored as bf16 - the bf16 ENC launch of the
-        //  2 000 tuples alone took 15 us)
-        // ... and where table_fused_tile fits, the same workgroups run conv1's projections of their encoder rows: the whole
-        // table inside this launch
-        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n) && encoder_fuses(w);
-        fused_table = fused_enc && table_fuses(w) && !gemm_tuning().no_fused_table;
-        const PlanListsArgs pa{obs, (int)bs, n, obs_stride, node_cols, L.plan, row_offsets_out, tconv ? 0 : 1, inline_scan, table ? T : 0};
+        const PlanListsArgs pa{obs, (int)bs, n, obs_stride, node_cols, L.plan, row_offsets_out, z.tconv ? 0 : 1, inline_scan, table ? T : 0};
         if (fused_table) {
-            const TableArgs ta = fused_table_args(w, pw, n, FeatureTables{L.h0, L.xl1, L.xr1});
+            const TableArgs ta = fused_table_args(w, pw, n, ft);
             const int tiles = table_items(ta);
             if (n > 64) MEL_LAUNCH((plan_enc_kernel<2, true>), dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, ta, tiles);
             else MEL_LAUNCH((plan_enc_kernel<1, true>), dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, ta, tiles);
         } else if (fused_enc) {
-            GemmArgs g;
-            g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-            g.W = bf ? w->encoder.layer[1].weight : pw.enc1, g.bias = w->encoder.layer[1].bias, g.y_bf16 = bf;
-            g.Y = L.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-            GemmRequest rq;                         // the 64 x 64 tiles of gemm_f32_kernel, one workgroup each
-            rq.mode = GEMM_MODE_ENC, rq.force_tile = MEL_TILE_64;
-            const GemmPlan enc = plan_gemm(&g, nullptr, 1, rq);
-            if (enc.status) return fail(enc.status, "encoder (feature tuples): %s", enc.why);
-            const int tiles = enc.grid;
-            if (n > 64) MEL_LAUNCH(plan_enc_kernel<2>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
-            else MEL_LAUNCH(plan_enc_kernel<1>, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, tiles);
+            GemmPlan enc;
+            if (mel_status st = plan_encoder_beside_plan(w, pw, z, n, L.h0, enc)) return st;
+            if (n > 64) MEL_LAUNCH(plan_enc_kernel<2>, dim3(enc.grid + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, enc.grid);
+            else MEL_LAUNCH(plan_enc_kernel<1>, dim3(enc.grid + (int)((bs + 3) / 4)), dim3(256), 0, s, pa, enc.batch, enc.grid);
         } else {
             with_words(n, [&](auto w) { MEL_LAUNCH(plan_lists_kernel<decltype(w)::value>, dim3((bs + 3) / 4), dim3(256), 0, s, pa); });
         }
         if (mel_status st = check_launch("plan_lists")) return st;
     }
-    {   // encoder on the U2 rows: relu(W1 relu(W0 x + b0) + b1)      (l_dgn.py:117-118)
-        GemmArgs g;
-        g.obs = obs, g.obs_width = obs_stride, g.n_nodes = n, g.in_dim = w->in_dim, g.node_cols = node_cols;
-        g.nid = L.plan.nid2, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
-        g.Y = L.h0, g.ldy = hidden, g.M = U2, g.M_dev = n2, g.N = hidden;
-        g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-        StageScope t(MEL_STAGE_ENCODER, s);
-        if (!table)
-            if (mel_status st = launch_encoder(g, L.enc0, s, "encoder", hint2)) return st;
-    }
-    // table mode: one row per feature tuple, evaluated here (every call) unless the caller prepared them for these weights
-    FeatureTables ft{L.h0, L.xl1, L.xr1};
-    if (table) {
-        if (w->tables && w->tables_nodes == n) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
-        else if (fused_table) {}        // the plan launch made all three
-        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
-    }
-    {   // conv1.lin_l on the U2 rows + conv1.lin_r on the U1 rows, one grouped launch
-        GemmArgs g[2];
-        g[0].bf16 = g[1].bf16 = bf, g[0].split = g[1].split = split_k(sp, hidden);
-        g[0].A = L.h0, g[0].lda = hidden, g[0].W = pw.c1l, g[0].bias = w->conv1.lin_l.bias;
-        g[0].Y = L.xl1, g[0].ldy = srcw, g[0].M = U2, g[0].M_dev = n2, g[0].N = srcw, g[0].K = hidden;
-        if (tconv)       // key | value of the sources in one problem (weights split along n)
-            g[0].W_hi = pw.c1v, g[0].bias_hi = w->conv1.lin_v.bias, g[0].split_n = hc;
-        g[1].A = L.h0, g[1].lda = hidden, g[1].arow = L.plan.arow1;
-        g[1].W = pw.c1r, g[1].bias = w->conv1.lin_r.bias;
-        g[1].Y = L.xr1, g[1].ldy = hc, g[1].M = U1, g[1].M_dev = n1, g[1].N = hc, g[1].K = hidden;
+    if (!table) {       // encoder on the U2 rows, then conv1.lin_l on the U2 rows + lin_r on the U1 rows in one grouped launch
+        GemmArgs e = encoder_on_rows(w, pw, z, obs, obs_stride, n, L.h0), g[2];
+        e.nid = L.plan.nid2, e.M = U2, e.M_dev = n2;
+        conv1_pair(w, pw, z, ft, g);
+        g[0].M = U2, g[0].M_dev = n2, g[1].arow = L.plan.arow1, g[1].M = U1, g[1].M_dev = n1;
         const long hints[2] = {hint2, hint1};
+        if (mel_status st = launch_encoder(e, L.enc0, s, "encoder", hint2)) return st;
         StageScope t(MEL_STAGE_CONV1_LIN, s);
-        if (!table)
-            if (mel_status st = launch_gemm_group(g, hints, 2, s, "conv1.lin_l + lin_r", 1)) return st;
+        if (mel_status st = launch_gemm_group(g, hints, 2, s, "conv1.lin_l + lin_r", 1)) return st;
+    } else if (!tables_prepared(w, n) && !fused_table) {        // (else the caller prepared the table, or the plan launch made all of it)
+        if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
     }
     {   // conv1 attention for the U1 targets; also drops x_1 and x_2 of every agent into the head input
         AttArgs a{};
-        a.xl = ft.xl, a.ld_l = srcw, a.xr = ft.xr, a.ld_r = hc, a.att = w->conv1.att, a.bias = w->conv1.bias;
-        a.kind = w->conv1.kind, a.score_scale = 1.0f / sqrtf((float)w->conv1.channels), a.bf16 = bf;
+        a.xl = ft.xl, a.ld_l = z.srcw, a.xr = ft.xr, a.ld_r = z.hc, a.att = w->conv1.att, a.bias = w->conv1.bias;
+        a.kind = w->conv1.kind, a.score_scale = 1.0f / sqrtf((float)w->conv1.channels), a.bf16 = z.bf;
         a.adj = L.plan.adj, a.bs = (int)bs, a.n = n;
         a.desc = L.plan.desc1, a.rows_dev = n1, a.rows_cap = U1, a.rows_hint = hint1;
-        a.out = L.h1, a.ldo = hc, a.xcat = L.xcat, a.ld_cat = latent, a.hidden = hidden, a.h0 = ft.h0;
+        a.out = L.h1, a.ldo = z.hc, a.xcat = L.xcat, a.ld_cat = z.latent, a.hidden = z.hidden, a.h0 = ft.h0;
         if (conv2.kernel == GemmKernel::PLANES) a.out_planes = reinterpret_cast<uint16_t*>(L.h1);
         a.out_scale = L.plan.dm1;       // the decision-maker mask (l_dgn.py:128) is applied as h1 is stored; x_2 is taken before it
         a.fid = table ? L.plan.fid : nullptr;
@@ -763,16 +787,54 @@ static mel_status ldgn_forward_impl(const mel_weights* w, const float* obs, cons
     }
     {   // conv2 attention, one target per agent row -> x_3
         AttArgs a{};
-        a.xl = L.xl2, a.ld_l = srcw, a.xr = L.xr2, a.ld_r = hc, a.att = w->conv2.att, a.bias = w->conv2.bias;
-        a.kind = w->conv2.kind, a.score_scale = 1.0f / sqrtf((float)w->conv2.channels), a.bf16 = bf;
+        a.xl = L.xl2, a.ld_l = z.srcw, a.xr = L.xr2, a.ld_r = z.hc, a.att = w->conv2.att, a.bias = w->conv2.bias;
+        a.kind = w->conv2.kind, a.score_scale = 1.0f / sqrtf((float)w->conv2.channels), a.bf16 = z.bf;
         a.adj = L.plan.adj;
         a.bs = (int)bs, a.n = n;
         a.desc = L.plan.desc2, a.rows_dev = nL, a.rows_cap = R, a.rows_hint = hintL;
-        a.xcat = L.xcat, a.ld_cat = latent, a.cat_off = hidden + hc;
+        a.xcat = L.xcat, a.ld_cat = z.latent, a.cat_off = z.hidden + z.hc;
         StageScope t(MEL_STAGE_CONV2_ATT, s);
         if (mel_status st = launch_attend<ATT_SINGLE>(a, head_lanes(w->conv2.heads, w->conv2.channels), s, "conv2 attention")) return st;
     }
     return run_heads(w, pw, L, R, nL, hintL, logits, s, select);
+}
+
+// the entry points of the two-convolution networks: `model` is MEL_MODEL_LDGN or MEL_MODEL_DGNR
+static mel_status two_conv_forward(int model, const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_width,
+                                   float* logits, void* workspace, size_t ws_bytes, void* stream) {
+    if (mel_status st = validate(w, model, bs, n, obs_width, true)) return st;
+    return ldgn_forward_impl(w, obs, make_dims(bs, n, bs, true), obs_width, nullptr, logits, nullptr, nullptr,
+                             workspace, ws_bytes, static_cast<hipStream_t>(stream));
+}
+static mel_status two_conv_forward_agents(int model, const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_stride,
+                                          const uint64_t* agent_mask, int64_t rows_cap, float* logits, int32_t* row_offsets, const mel_select* select,
+                                          void* workspace, size_t ws_bytes, void* stream) {
+    if (mel_status st = validate(w, model, bs, n, obs_stride, false)) return st;
+    if (!agent_mask) return fail(MEL_ERR_INVALID_ARG, "agent_mask is null");
+    if (rows_cap < 1 || rows_cap > bs * (int64_t)n) return fail(MEL_ERR_INVALID_ARG, "rows_cap=%ld outside [1, bs*n]", (long)rows_cap);
+    if (select && !select->act) return fail(MEL_ERR_INVALID_ARG, "select->act is null");
+    return ldgn_forward_impl(w, obs, make_dims(bs, n, rows_cap, false), obs_stride, agent_mask, logits, row_offsets,
+                             select, workspace, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+// mel_prepare_feature_tables and mel_feature_tables_fused (`one_launch`): the table into the caller's buffer
+static mel_status feature_tables_entry(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, bool one_launch, hipStream_t s) {
+    if (mel_status st = validate(w, w ? w->model : 0, 1, n_nodes, n_nodes * ((w ? w->in_dim : 5) + 3), false)) return st;
+    if (one_launch && !table_fuses(w))
+        return fail(MEL_ERR_UNSUPPORTED, "the one-launch table is built for GATv2 L-DGN at f32 / f32-auto precision, hidden = %d", TBL_HIDDEN);
+    if (!one_launch && w->in_dim != 5) return fail(MEL_ERR_UNSUPPORTED, "the node-feature table is defined for the 5 GraphEnv features");
+    const size_t need = mel_feature_tables_bytes(w, n_nodes);
+    if (!tables || bytes < need) return fail(MEL_ERR_WORKSPACE, "feature-table buffer %zu < %zu bytes", bytes, need);
+    if (w->precision != MEL_PREC_F32 && !w->prepared)
+        return fail(MEL_ERR_INVALID_ARG, "bf16 / split precision: prepare the weights first (mel_prepare_weights)");
+    clear_stale_error();
+    ProjWeights pw, pw_alt;
+    if (mel_status st = resolve_projections(w, FwdLayout{}, pw, pw_alt, s)) return st;
+    const FeatureTables t = carve_tables(w, n_nodes, tables, nullptr);
+    if (!one_launch) return run_feature_tables(w, pw, n_nodes, t, s);
+    const TableArgs ta = fused_table_args(w, pw, n_nodes, t);
+    MEL_LAUNCH(table_fused_kernel, dim3(table_items(ta)), dim3(256), 0, s, ta);
+    return check_launch("feature tables, one launch");
 }
 
 }  // namespace mel
@@ -831,35 +893,11 @@ size_t mel_feature_tables_bytes(const mel_weights* w, int32_t n_nodes) {
 }
 
 mel_status mel_prepare_feature_tables(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, void* stream) {
-    if (mel_status st = validate(w, w ? w->model : 0, 1, n_nodes, n_nodes * ((w ? w->in_dim : 5) + 3), false)) return st;
-    if (w->in_dim != 5) return fail(MEL_ERR_UNSUPPORTED, "the node-feature table is defined for the 5 GraphEnv features");
-    const size_t need = mel_feature_tables_bytes(w, n_nodes);
-    if (!tables || bytes < need) return fail(MEL_ERR_WORKSPACE, "feature-table buffer %zu < %zu bytes", bytes, need);
-    if (w->precision != MEL_PREC_F32 && !w->prepared)
-        return fail(MEL_ERR_INVALID_ARG, "bf16 / split precision: prepare the weights first (mel_prepare_weights)");
-    clear_stale_error();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ProjWeights pw, pw_alt;
-    FwdLayout none{};
-    if (mel_status st = resolve_projections(w, none, pw, pw_alt, s)) return st;
-    return run_feature_tables(w, pw, n_nodes, carve_tables(w, n_nodes, tables, nullptr), s);
+    return feature_tables_entry(w, n_nodes, tables, bytes, false, static_cast<hipStream_t>(stream));
 }
 
 mel_status mel_feature_tables_fused(const mel_weights* w, int32_t n_nodes, void* tables, size_t bytes, void* stream) {
-    if (mel_status st = validate(w, w ? w->model : 0, 1, n_nodes, n_nodes * ((w ? w->in_dim : 5) + 3), false)) return st;
-    if (!table_fuses(w)) return fail(MEL_ERR_UNSUPPORTED, "the one-launch table is built for GATv2 L-DGN at f32 / f32-auto precision, hidden = %d", TBL_HIDDEN);
-    const size_t need = mel_feature_tables_bytes(w, n_nodes);
-    if (!tables || bytes < need) return fail(MEL_ERR_WORKSPACE, "feature-table buffer %zu < %zu bytes", bytes, need);
-    if (w->precision != MEL_PREC_F32 && !w->prepared)
-        return fail(MEL_ERR_INVALID_ARG, "bf16 / split precision: prepare the weights first (mel_prepare_weights)");
-    clear_stale_error();
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    ProjWeights pw, pw_alt;
-    FwdLayout none{};
-    if (mel_status st = resolve_projections(w, none, pw, pw_alt, s)) return st;
-    const TableArgs ta = fused_table_args(w, pw, n_nodes, carve_tables(w, n_nodes, tables, nullptr));
-    MEL_LAUNCH(table_fused_kernel, dim3(table_items(ta)), dim3(256), 0, s, ta);
-    return check_launch("feature tables, one launch");
+    return feature_tables_entry(w, n_nodes, tables, bytes, true, static_cast<hipStream_t>(stream));
 }
 
 mel_status mel_prepare_weights(const mel_weights* w, void* prepared, size_t bytes, void* stream) {
@@ -885,40 +923,26 @@ size_t mel_workspace_bytes_agents(const mel_weights* w, int64_t bs, int32_t n_no
 
 mel_status mel_ldgn_forward(const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_width,
                             float* logits, void* workspace, size_t ws_bytes, void* stream) {
-    if (mel_status st = validate(w, MEL_MODEL_LDGN, bs, n, obs_width, true)) return st;
-    return ldgn_forward_impl(w, obs, make_dims(bs, n, bs, true), obs_width, nullptr, logits, nullptr, nullptr,
-                             workspace, ws_bytes, static_cast<hipStream_t>(stream));
+    return two_conv_forward(MEL_MODEL_LDGN, w, obs, bs, n, obs_width, logits, workspace, ws_bytes, stream);
 }
 
 mel_status mel_ldgn_forward_agents(const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_stride,
                                    const uint64_t* agent_mask, int64_t rows_cap, float* logits,
                                    int32_t* row_offsets, const mel_select* select, void* workspace,
                                    size_t ws_bytes, void* stream) {
-    if (mel_status st = validate(w, MEL_MODEL_LDGN, bs, n, obs_stride, false)) return st;
-    if (!agent_mask) return fail(MEL_ERR_INVALID_ARG, "agent_mask is null");
-    if (rows_cap < 1 || rows_cap > bs * (int64_t)n) return fail(MEL_ERR_INVALID_ARG, "rows_cap=%ld outside [1, bs*n]", (long)rows_cap);
-    if (select && !select->act) return fail(MEL_ERR_INVALID_ARG, "select->act is null");
-    return ldgn_forward_impl(w, obs, make_dims(bs, n, rows_cap, false), obs_stride, agent_mask, logits, row_offsets,
-                             select, workspace, ws_bytes, static_cast<hipStream_t>(stream));
+    return two_conv_forward_agents(MEL_MODEL_LDGN, w, obs, bs, n, obs_stride, agent_mask, rows_cap, logits, row_offsets, select, workspace, ws_bytes, stream);
 }
 
 mel_status mel_dgnr_forward(const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_width,
                             float* logits, void* workspace, size_t ws_bytes, void* stream) {
-    if (mel_status st = validate(w, MEL_MODEL_DGNR, bs, n, obs_width, true)) return st;
-    return ldgn_forward_impl(w, obs, make_dims(bs, n, bs, true), obs_width, nullptr, logits, nullptr, nullptr,
-                             workspace, ws_bytes, static_cast<hipStream_t>(stream));
+    return two_conv_forward(MEL_MODEL_DGNR, w, obs, bs, n, obs_width, logits, workspace, ws_bytes, stream);
 }
 
 mel_status mel_dgnr_forward_agents(const mel_weights* w, const float* obs, int64_t bs, int32_t n, int32_t obs_stride,
                                    const uint64_t* agent_mask, int64_t rows_cap, float* logits,
                                    int32_t* row_offsets, const mel_select* select, void* workspace,
                                    size_t ws_bytes, void* stream) {
-    if (mel_status st = validate(w, MEL_MODEL_DGNR, bs, n, obs_stride, false)) return st;
-    if (!agent_mask) return fail(MEL_ERR_INVALID_ARG, "agent_mask is null");
-    if (rows_cap < 1 || rows_cap > bs * (int64_t)n) return fail(MEL_ERR_INVALID_ARG, "rows_cap=%ld outside [1, bs*n]", (long)rows_cap);
-    if (select && !select->act) return fail(MEL_ERR_INVALID_ARG, "select->act is null");
-    return ldgn_forward_impl(w, obs, make_dims(bs, n, rows_cap, false), obs_stride, agent_mask, logits, row_offsets,
-                             select, workspace, ws_bytes, static_cast<hipStream_t>(stream));
+    return two_conv_forward_agents(MEL_MODEL_DGNR, w, obs, bs, n, obs_stride, agent_mask, rows_cap, logits, row_offsets, select, workspace, ws_bytes, stream);
 }
 
 static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, const float* obs, int64_t bs, int32_t n,
@@ -933,15 +957,15 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
     hipStream_t s = static_cast<hipStream_t>(stream);
     clear_stale_error();
     const int node_cols = w->in_dim + 3;
-    const int hidden = w->encoder.layer[1].out_dim, hc = w->conv1.heads * w->conv1.channels;
-    const int M = (int)(bs * n);
-    const int bf = w->precision == MEL_PREC_BF16;
-    const int sp = w->precision == MEL_PREC_F32_SPLIT;
+    const NetShape z = shape_of(w);
+    const int hc = z.hc, bf = z.bf, M = (int)(bs * n);
     ProjWeights pw, pw_alt;
     if (mel_status st = resolve_projections(w, L, pw, pw_alt, s)) return st;
-    const int T = n * FEATURE_TUPLES_PER_DEGREE;      // node-feature table (plan_masks.hpp): every node is a row here
-    const bool table = (w->flags & MEL_FWD_INTEGER_FEATURES) && w->in_dim == 5 && M >= 2L * T;
-    bool fused_enc = false;
+    const int T = n * FEATURE_TUPLES_PER_DEGREE;
+    const bool table = takes_table(w, n, M);           // (every node is a row here)
+    const bool fused_enc = encoder_rides_in_plan(w, z, n, table);
+    FeatureTables ft{L.h0, L.xl1, nullptr};            // (the workspace's rows, unless the caller prepared tables)
+    if (table && tables_prepared(w, n)) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
 
     {
         StageScope t(MEL_STAGE_PLAN, s);
@@ -953,51 +977,25 @@ static mel_status hldgn_forward_impl(const mel_weights* w, int32_t aggregator, c
             });
             if (mel_status st = check_launch("plan_masks")) return st;
         }
-        // fp32 + node-feature table evaluated by this call: the tuple ids and the encoder rows of the tuples are independent
-        // (the table depends on the weights only) - one launch runs both, as plan_enc_kernel does for L-DGN
-        fused_enc = table && !sp && !(w->tables && w->tables_nodes == n) && encoder_fuses(w);
         if (fused_enc) {
-            GemmArgs g;
-            g.feat_domain = 1, g.in_dim = w->in_dim, g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-            g.W = bf ? w->encoder.layer[1].weight : pw.enc1, g.bias = w->encoder.layer[1].bias, g.y_bf16 = bf;
-            g.Y = L.h0, g.ldy = hidden, g.M = T, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-            GemmRequest rq;                         // the 64 x 64 tiles of gemm_f32_kernel, one workgroup each
-            rq.mode = GEMM_MODE_ENC, rq.force_tile = MEL_TILE_64;
-            const GemmPlan enc = plan_gemm(&g, nullptr, 1, rq);
-            if (enc.status) return fail(enc.status, "encoder (feature tuples): %s", enc.why);
-            const int tiles = enc.grid;
-            MEL_LAUNCH(fid_enc_kernel, dim3(tiles + (int)((bs + 3) / 4)), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols, L.plan, T,
-                       enc.batch, tiles);
+            GemmPlan enc;
+            if (mel_status st = plan_encoder_beside_plan(w, pw, z, n, L.h0, enc)) return st;
+            MEL_LAUNCH(fid_enc_kernel, dim3(enc.grid + (int)((bs + 3) / 4)), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols, L.plan, T,
+                       enc.batch, enc.grid);
         } else {
             MEL_LAUNCH(feature_ids_kernel, dim3((bs + 3) / 4), dim3(256), 0, s, obs, (int)bs, n, obs_width, node_cols, L.plan,
                        table ? T : 0);
         }
         if (mel_status st = check_launch("feature_ids")) return st;
     }
-    {
-        GemmArgs g;
-        g.obs = obs, g.obs_width = obs_width, g.n_nodes = n, g.in_dim = w->in_dim, g.node_cols = node_cols;
-        g.enc_w = w->encoder.layer[0].weight, g.enc_b = w->encoder.layer[0].bias;
-        g.W = pw.enc1, g.bias = w->encoder.layer[1].bias, g.bf16 = bf, g.split = split_k(sp, w->encoder.layer[0].out_dim);
-        g.Y = L.h0, g.ldy = hidden, g.M = M, g.N = hidden, g.K = w->encoder.layer[0].out_dim, g.relu = 1;
-        StageScope t(MEL_STAGE_ENCODER, s);
-        if (!table)
-            if (mel_status st = launch_encoder(g, L.enc0, s, "encoder")) return st;
-    }
-    {   // x_l | x_r for every node in one GEMM (weights split along n)
-        GemmArgs g;
-        g.A = L.h0, g.lda = hidden;
-        g.W = pw.c1l, g.W_hi = pw.c1r, g.bf16 = bf, g.split = split_k(sp, hidden);
-        g.bias = w->conv1.lin_l.bias, g.bias_hi = w->conv1.lin_r.bias, g.split_n = hc;
-        g.Y = L.xl1, g.ldy = 2 * hc, g.M = M, g.N = 2 * hc, g.K = hidden;
+    if (!table) {       // encoder, then x_l | x_r, on every node
+        GemmArgs e = encoder_on_rows(w, pw, z, obs, obs_width, n, L.h0), g = conv1_hl(w, pw, z, ft);
+        e.M = g.M = M;
+        if (mel_status st = launch_encoder(e, L.enc0, s, "encoder")) return st;
         StageScope t(MEL_STAGE_CONV1_LIN, s);
-        if (!table)
-            if (mel_status st = launch_gemm(g, GEMM_MODE_PLAIN, s, "conv1.lin_l|lin_r")) return st;
-    }
-    FeatureTables ft{L.h0, L.xl1, nullptr};
-    if (table) {
-        if (w->tables && w->tables_nodes == n) ft = carve_tables(w, n, const_cast<void*>(w->tables), nullptr);
-        else if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
+        if (mel_status st = launch_gemm(g, GEMM_MODE_PLAIN, s, "conv1.lin_l|lin_r")) return st;
+    } else if (!tables_prepared(w, n)) {
+        if (mel_status st = run_feature_tables(w, pw, n, ft, s, /*encoder_done=*/fused_enc, L.enc0)) return st;
     }
     {
         AttArgs a{};

@@ -215,15 +215,15 @@ class HipForwardMixin:
         vsum = 0
         for p in plist:
             vsum += p._version
-        stamp = (vsum, self.feature_dtype, self.prepared_tables, id(getattr(self, "_prepared", None)), id(getattr(self, "_tables", None)))
-        if getattr(self, "_ensure_stamp", None) == stamp:
+        stamp = lambda: (vsum, self.feature_dtype, self.prepared_tables, id(getattr(self, "_prepared", None)),
+                         id(getattr(self, "_tables", None)))
+        if getattr(self, "_ensure_stamp", None) == stamp():
             return
         device = device if device is not None else plist[0].device
         w = self._weights()
         self._refresh_prepared(w, device)
         self._refresh_tables(w, device)
-        self._ensure_stamp = (vsum, self.feature_dtype, self.prepared_tables, id(getattr(self, "_prepared", None)),
-                              id(getattr(self, "_tables", None)))
+        self._ensure_stamp = stamp()            # (taken again: the refreshes may have replaced the caches)
 
     def mark_weights_changed(self) -> None:
         """The parameters were changed behind torch's version counters (an optimizer step replayed from a HIP graph): the next
@@ -261,22 +261,39 @@ class HipForwardMixin:
         self._w_cache = (key, w)
         return w
 
-    def _workspace(self, w, bs: int, device) -> torch.Tensor:
-        lib = _lib.load()
-        need = int(lib.mel_workspace_bytes(C.byref(w), bs, self.agents_num))
-        if need == 0:
-            raise RuntimeError("mel_workspace_bytes rejected the configuration")
-        ws = getattr(self, "_ws", None)
+    def _grown(self, attr: str, need: int, device) -> torch.Tensor:
+        """The module's own scratch ``attr`` (``_ws``: hip_forward / hip_forward_envs, ``_ws_agents``), replaced when too small."""
+        ws = getattr(self, attr, None)
         if ws is None or ws.numel() < need or ws.device != device:
             ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws = ws
+            setattr(self, attr, ws)
         return ws
+
+    def _workspace(self, w, bs: int, device) -> torch.Tensor:
+        need = int(_lib.load().mel_workspace_bytes(C.byref(w), bs, self.agents_num))
+        if need == 0:
+            raise RuntimeError("mel_workspace_bytes rejected the configuration")
+        return self._grown("_ws", need, device)
+
+    def _call(self, device, plan_ready: bool, integer_features: bool, what: str, call):
+        """What every dispatcher does around its entry point: the cached struct with the prepared weights and tables of this
+        weight version, ``w.flags`` set for ``call(lib, w) -> status`` ALONE - the struct is cached, so they are reset even when
+        the call raises - and the status checked under the name ``what``.
+        plan_ready: mel_env_round's plan sink wrote this call's masks; integer_features: the obs rows come from the env."""
+        w = self._weights()
+        self._refresh_prepared(w, device)
+        self._refresh_tables(w, device)
+        w.flags = self._forward_flags(plan_ready, integer_features)
+        try:
+            st = call(_lib.load(), w)
+        finally:
+            w.flags = 0
+        _lib.check(st, what)
 
     def hip_forward(self, obs: torch.Tensor, out: torch.Tensor | None = None, integer_features: bool = False) -> torch.Tensor:
         """Inference through libmelissa_hip.so on the current HIP stream.  obs: CUDA float32 [bs, 8N+1].
         ``integer_features``: the caller guarantees the observations come from the env (node features are the integers
         GraphEnv writes), which lets large batches go through the node-feature table (MEL_FWD_INTEGER_FEATURES)."""
-        lib = _lib.load()
         if not obs.is_cuda:
             raise RuntimeError("the HIP forward needs the observation on a ROCm device; there is no CPU "
                                "fallback (use torch_forward for autograd on any device)")
@@ -286,24 +303,18 @@ class HipForwardMixin:
         bs = obs.shape[0]
         if bs == 0:             # an empty batch has empty logits (nothing to launch), as the torch ops of the reference give
             return out if out is not None else torch.empty(0, self.output_dim, dtype=torch.float32, device=obs.device)
-        w = self._weights()
-        self._refresh_prepared(w, obs.device)
-        self._refresh_tables(w, obs.device)
-        ws = self._workspace(w, bs, obs.device)
         if out is None:
             out = torch.empty(bs, self.output_dim, dtype=torch.float32, device=obs.device)
-        stream = _lib.current_stream_ptr(obs.device)
-        w.flags = self._forward_flags(False, integer_features)
-        if self._MODEL in (_lib.MODEL_LDGN, _lib.MODEL_DGNR):
-            fn = lib.mel_ldgn_forward if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward
-            st = fn(C.byref(w), obs.data_ptr(), bs, self.agents_num, obs.shape[1], out.data_ptr(), ws.data_ptr(),
-                    ws.numel(), stream)
-        else:
-            st = lib.mel_hldgn_forward(C.byref(w), _lib.AGG[self.aggregator_name], obs.data_ptr(), bs,
-                                       self.agents_num, obs.shape[1], out.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), stream)
-        w.flags = 0
-        _lib.check(st, type(self).__name__ + ".forward")
+
+        def call(lib, w):
+            ws = self._workspace(w, bs, obs.device)
+            tail = (obs.data_ptr(), bs, self.agents_num, obs.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(),
+                    _lib.current_stream_ptr(obs.device))
+            if self._MODEL == _lib.MODEL_HLDGN:
+                return lib.mel_hldgn_forward(C.byref(w), _lib.AGG[self.aggregator_name], *tail)
+            return (lib.mel_ldgn_forward if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward)(C.byref(w), *tail)
+
+        self._call(obs.device, False, integer_features, type(self).__name__ + ".forward", call)
         return out
 
     def hip_tap(self, kind: int, bs: int, rows_cap: int = 0, workspace: torch.Tensor | None = None) -> torch.Tensor:
@@ -342,29 +353,22 @@ class HipForwardMixin:
         ``live`` / ``n_nodes`` set): the per-(env, agent) argmax / eps-greedy fused into the launch that writes the logits."""
         if self._MODEL != _lib.MODEL_HLDGN:
             raise RuntimeError("hip_forward_envs is the HL-DGN entry point")
-        lib = _lib.load()
         assert obs_matrix.is_cuda and obs_matrix.dtype == torch.float32 and obs_matrix.stride(-1) == 1
-        bs = obs_matrix.shape[0]
-        w = self._weights()
-        self._refresh_prepared(w, obs_matrix.device)
-        self._refresh_tables(w, obs_matrix.device)
-        ws = workspace if workspace is not None else self._workspace(w, bs, obs_matrix.device)
+        bs, device = obs_matrix.shape[0], obs_matrix.device
         if out is None:
-            out = torch.empty(bs, self.output_dim, dtype=torch.float32, device=obs_matrix.device)
-        # (the struct is cached: always set, never left behind)
-        w.flags = self._forward_flags(plan_ready, integer_features)
-        if select is not None:
-            st = lib.mel_hldgn_forward_envs_select(C.byref(w), _lib.AGG[self.aggregator_name], obs_matrix.data_ptr(), bs,
-                                                   self.agents_num, obs_matrix.stride(0), out.data_ptr(), C.byref(select),
-                                                   ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(obs_matrix.device))
-            w.flags = 0
-            _lib.check(st, "mel_hldgn_forward_envs_select")
-            return out
-        st = lib.mel_hldgn_forward_envs(C.byref(w), _lib.AGG[self.aggregator_name], obs_matrix.data_ptr(), bs,
-                                        self.agents_num, obs_matrix.stride(0), out.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), _lib.current_stream_ptr(obs_matrix.device))
-        w.flags = 0
-        _lib.check(st, "mel_hldgn_forward_envs")
+            out = torch.empty(bs, self.output_dim, dtype=torch.float32, device=device)
+
+        def call(lib, w):
+            ws = workspace if workspace is not None else self._workspace(w, bs, device)
+            head = (C.byref(w), _lib.AGG[self.aggregator_name], obs_matrix.data_ptr(), bs, self.agents_num, obs_matrix.stride(0),
+                    out.data_ptr())
+            tail = (ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(device))
+            if select is not None:
+                return lib.mel_hldgn_forward_envs_select(*head, C.byref(select), *tail)
+            return lib.mel_hldgn_forward_envs(*head, *tail)
+
+        self._call(device, plan_ready, integer_features,
+                   "mel_hldgn_forward_envs_select" if select is not None else "mel_hldgn_forward_envs", call)
         return out
 
     def agents_workspace_bytes(self, bs: int, rows_cap: int) -> int:
@@ -381,34 +385,24 @@ class HipForwardMixin:
         patterns ([bs, 2] words beyond 64 nodes).  Returns (logits [rows_cap, A] - rows ordered by env then agent id -, row_offsets [bs+1])."""
         if self._MODEL == _lib.MODEL_HLDGN:
             raise RuntimeError("hip_forward_agents is the L-DGN / DGN-R entry point")
-        lib = _lib.load()
         assert obs_matrix.is_cuda and obs_matrix.dtype == torch.float32 and obs_matrix.stride(-1) == 1
-        bs = obs_matrix.shape[0]
-        w = self._weights()
-        self._refresh_prepared(w, obs_matrix.device)
-        self._refresh_tables(w, obs_matrix.device)
-        need = int(lib.mel_workspace_bytes_agents(C.byref(w), bs, self.agents_num, rows_cap))
-        if workspace is not None:                  # caller-owned scratch (one per concurrent stream)
-            ws = workspace
-            if ws.numel() < need:
-                raise RuntimeError(f"workspace of {ws.numel()} bytes < {need} needed")
-        else:
-            ws = getattr(self, "_ws_agents", None)
-            if ws is None or ws.numel() < need or ws.device != obs_matrix.device:
-                ws = torch.empty(need, dtype=torch.uint8, device=obs_matrix.device)
-                self._ws_agents = ws
+        bs, device = obs_matrix.shape[0], obs_matrix.device
         if out is None:
-            out = torch.empty(rows_cap, self.output_dim, dtype=torch.float32, device=obs_matrix.device)
+            out = torch.empty(rows_cap, self.output_dim, dtype=torch.float32, device=device)
         if row_offsets is None:
-            row_offsets = torch.empty(bs + 1, dtype=torch.int32, device=obs_matrix.device)
-        fn = lib.mel_ldgn_forward_agents if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward_agents
-        # plan_ready: mel_env_round's plan sink wrote this call's masks; integer_features: obs rows come from the env
-        w.flags = self._forward_flags(plan_ready, integer_features)
-        st = fn(C.byref(w), obs_matrix.data_ptr(), bs, self.agents_num, obs_matrix.stride(0), agent_mask.data_ptr(),
-                rows_cap, out.data_ptr(), row_offsets.data_ptr(), C.byref(select) if select is not None else None,
-                ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(obs_matrix.device))
-        w.flags = 0
-        _lib.check(st, "mel_ldgn_forward_agents")
+            row_offsets = torch.empty(bs + 1, dtype=torch.int32, device=device)
+
+        def call(lib, w):
+            need = int(lib.mel_workspace_bytes_agents(C.byref(w), bs, self.agents_num, rows_cap))
+            if workspace is not None and workspace.numel() < need:           # caller-owned scratch (one per concurrent stream)
+                raise RuntimeError(f"workspace of {workspace.numel()} bytes < {need} needed")
+            ws = workspace if workspace is not None else self._grown("_ws_agents", need, device)
+            fn = lib.mel_ldgn_forward_agents if self._MODEL == _lib.MODEL_LDGN else lib.mel_dgnr_forward_agents
+            return fn(C.byref(w), obs_matrix.data_ptr(), bs, self.agents_num, obs_matrix.stride(0), agent_mask.data_ptr(),
+                      rows_cap, out.data_ptr(), row_offsets.data_ptr(), C.byref(select) if select is not None else None,
+                      ws.data_ptr(), ws.numel(), _lib.current_stream_ptr(device))
+
+        self._call(device, plan_ready, integer_features, "mel_ldgn_forward_agents", call)
         return out, row_offsets
 
     def _prepare_obs(self, obs):
