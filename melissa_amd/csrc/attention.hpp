@@ -405,7 +405,8 @@ constexpr int ATT_PROF_MODE = MEL_ATT_PROF;
 constexpr int ATT_PROF_MODE = -1;      // no kernel has it
 #endif
 // Tuning builds (-DMEL_ATT_PROF=<MODE>, kprof.hpp): cycles per sampled wave (wave 0 of every 32nd workgroup) of the rows kernel with that MODE (0 = conv1, 2 = conv2) in
-// [0] prologue (row count, att / bias), [1] descriptor load, [2] attend_target (row loads + scores + softmax + sum),
+// [0] prologue (row count, att / bias; the first row's descriptor is requested with them), [1] what is left to wait for the
+// descriptor, [2] attend_target (row loads + scores + softmax + sum),
 // [3] stores, [4] whole wave, [5] waves counted, [6] rows processed
 __device__ unsigned long long g_att_prof[8];
 
@@ -427,28 +428,29 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
     KLaps<MODE == ATT_PROF_MODE && !BF, 8> prof;
     const auto wave_start = prof.mark();
     const int lane = lane_id();
-    const int rows = min(*a.rows_dev, a.rows_cap);
     constexpr int LIVE = att_live_lanes<FORM>();
-    const Vec<VPL> att = load_vec_or_zero<VPL, LIVE>(a.att, lane);
-    const Vec<VPL> bias = load_vec_or_zero<VPL, LIVE>(a.bias, lane);
-    // grid-stride over the target rows: the grid is sized from the expected row count, not the worst case
-    // (a surplus workgroup costs a global-load latency and a CU slot before it can exit)
-    // XCD-aware order: consecutive target rows belong to one env and share their source rows, so each XCD
-    // (block id % 8 under round-robin dispatch; the grid is a multiple of 8) walks a CONTIGUOUS range of rows
-    // and the shared rows hit in that XCD's L2 instead of being fetched by all eight (measured before the
-    // remap: 54 % L2 misses in this kernel).
-    prof.lap(0, att.v[0], bias.v[0], ksgpr(rows));
-    const int per_xcd = gridDim.x >> 3;
-    const int vblock = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    const int rows_pad = ((rows + 4 * (int)gridDim.x - 1) / (4 * (int)gridDim.x)) * (4 * (int)gridDim.x);
-    const int span = rows_pad >> 3;              // rows each XCD owns (multiple of 4 * per_xcd)
+    // A wave takes the rows slot, slot + 4 * grid, ...: the grid is sized from the expected row count (with a quarter to spare),
+    // not the worst case, so a wave has one row, seldom more (a surplus workgroup costs a global-load latency and a CU slot
+    // before it can exit).  XCD-aware slots: consecutive target rows belong to one env and share their source rows, so the
+    // workgroups of an XCD (block id % 8 under round-robin dispatch; the grid is a multiple of 8) hold a CONTIGUOUS range of
+    // slots and the shared rows hit in that XCD's L2 instead of being fetched by all eight (measured before the remap: 54 %
+    // L2 misses in this kernel).
     // the wave's number, and with it the row index and everything addressed by it, in SGPRs
     const int wave = uniform_i32(threadIdx.x >> 6);
-    for (int i = (vblock % per_xcd) * 4 + wave; i < span; i += per_xcd * 4) {
-        const int r = (blockIdx.x & 7) * span + i;
-        if (r >= rows) continue;
+    const int stride = 4 * (int)gridDim.x;
+    int r = (((int)blockIdx.x & 7) * ((int)gridDim.x >> 3) + ((int)blockIdx.x >> 3)) * 4 + wave;
+    // The slot is known from the launch alone and the row count is a bound, not an address (the descriptors are allocated to
+    // rows_cap): the wave asks for its first row's descriptor TOGETHER with the count, att and bias - one memory latency
+    // instead of two in front of everything the descriptor addresses.  A slot past the count drops what it fetched.
+    const TargetDesc<W>* const desc = static_cast<const TargetDesc<W>*>(a.desc);
+    TargetDesc<W> d{};
+    if (r < a.rows_cap) d = desc[r];                 // one 32-byte record: no chain of dependent index loads
+    const int rows = min(*a.rows_dev, a.rows_cap);
+    const Vec<VPL> att = load_vec_or_zero<VPL, LIVE>(a.att, lane);
+    const Vec<VPL> bias = load_vec_or_zero<VPL, LIVE>(a.bias, lane);
+    prof.lap(0, att.v[0], bias.v[0], ksgpr(rows));
+    while (r < rows) {
         prof.mark();
-        const TargetDesc<W> d = static_cast<const TargetDesc<W>*>(a.desc)[r];   // one 32-byte record: no chain of dependent index loads
         prof.lap(1, ksgpr(d.sources.w[0]), ksgpr(d.soff));
         int my_fid[W];
         MEL_W_FOR(h) my_fid[h] = 0;
@@ -490,6 +492,8 @@ __global__ __launch_bounds__(256, MEL_ATT_MINB) void gat_attend_rows_kernel(AttA
         }
         prof.lap(3);
         prof.add(6, 1);
+        r += stride;
+        if (r < rows) d = desc[r];                   // (more rows than the grid was sized for)
     }
     prof.since(4, wave_start);
     prof.add(5, 1);
