@@ -334,6 +334,20 @@ mel_status mel_gat_backward(const float* xl, const float* xv, const float* xr, c
                             const float* out, const float* grad_out, int64_t bs, int32_t n_nodes, int32_t heads,
                             int32_t channels, int32_t kind, float* dxl, float* dxv, float* dxr, float* datt,
                             float* dbias, float* stats, void* stream);
+/* mel_gat_attention_weights: the softmax coefficients mel_gat_forward aggregates with and then drops - what upstream's
+ *   operators return under return_attention_weights=True.  alpha: device fp32 [bs * n_nodes, n_nodes, heads];
+ *   alpha[b*n + i, j, h] = weight of source node j of graph b for target node i and head h:
+ *     GATv2        j in adj(i) + {i} (self-loop added),  e_ij = att . leaky_relu(x_r[i] + x_l[j], 0.2)
+ *     Transformer  j in adj(i),                          e_ij = q[i] . k[j] / sqrt(channels)
+ *     alpha_ij = exp(e_ij - max_j e_ij) / (sum_j exp(e_ij - max_j e_ij) + 1e-16)
+ *   over the forward's sources in the forward's order, with the forward's score arithmetic.  xl = sources (keys), xr = targets
+ *   (queries), att [HC] (GATv2 only, else null); neither bias nor values: the coefficients do not depend on them.  EVERY element
+ *   is written - 0.0f where j is not a source of i, so a target without a source has a row of zeros and the caller never clears
+ *   alpha - and each exactly once (no atomics).  Takes every shape mel_gat_forward takes; bs * n_nodes^2 * heads > 2^31
+ *   elements is MEL_ERR_INVALID_ARG.  No gradient flows through it. */
+mel_status mel_gat_attention_weights(const float* xl, const float* xr, const float* att, const uint64_t* adj, int64_t bs,
+                                     int32_t n_nodes, int32_t heads, int32_t channels, int32_t kind, float* alpha,
+                                     void* stream);
 mel_status mel_pool_forward(const float* x, const float* dm, int64_t bs, int32_t n_nodes, int32_t hc,
                             int32_t aggregator, float* pooled, int32_t* arg, void* stream);
 mel_status mel_pool_backward(const float* grad_pooled, const float* dm, const int32_t* arg, int64_t bs,

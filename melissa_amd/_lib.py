@@ -37,7 +37,7 @@ SET_HAS_MESSAGE, SET_ORIGIN, SET_INTERESTED, SET_SCRIPTED, SET_TRUNCATED, SET_AL
     SET_AGENTS = range(8)
 
 # every symbol include/melissa_hip.h declares
-EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_tables", "mel_feature_tables_fused", "mel_prepared_weights_bytes", "mel_prepare_weights", "mel_transpose_f32", "mel_episode_refill", "mel_episode_test_seeds", "mel_abi_sizeof", "mel_radius_graph", "mel_gat_forward", "mel_gat_backward", "mel_pool_forward", "mel_pool_backward",
+EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_tables", "mel_feature_tables_fused", "mel_prepared_weights_bytes", "mel_prepare_weights", "mel_transpose_f32", "mel_episode_refill", "mel_episode_test_seeds", "mel_abi_sizeof", "mel_radius_graph", "mel_gat_forward", "mel_gat_backward", "mel_gat_attention_weights", "mel_pool_forward", "mel_pool_backward",
            "mel_gemm_bf16", "mel_convert_bf16", "mel_hldgn_forward_envs", "mel_hldgn_forward_envs_select", "mel_plan_pointers", "mel_select_action_envs", "mel_dgnr_forward", "mel_dgnr_forward_agents", "mel_gemm_f32", "mel_gemm_f32_t", "mel_gemm_f32_splitk", "mel_gemm_f32_split", "mel_replay_sample", "mel_replay_sample_prio", "mel_replay_update_priority", "mel_adam_step", "mel_workspace_bytes", "mel_workspace_bytes_agents", "mel_ldgn_forward_agents",
            "mel_select_action_rows", "mel_ldgn_forward", "mel_hldgn_forward", "mel_forward_tap",
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
@@ -218,6 +218,8 @@ def load(build_if_missing: bool = True):
     lib.mel_gat_forward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
     lib.mel_gat_backward.restype = i32
     lib.mel_gat_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mel_gat_attention_weights.restype = i32
+    lib.mel_gat_attention_weights.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]
     lib.mel_pool_forward.restype = i32
     lib.mel_pool_forward.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp]
     lib.mel_pool_backward.restype = i32

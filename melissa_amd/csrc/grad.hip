@@ -335,6 +335,53 @@ __global__ __launch_bounds__(256) void gat_backward_sources_kernel(GradArgs a) {
     if constexpr (KIND == MEL_CONV_TRANSFORMER) gstore_live<VPL, LIVE>(a.dxv + me, acc_v, lane);
 }
 
+// ---- the coefficients themselves: alpha[r, j, h] of gat_full_forward_kernel, for whoever asks which neighbours a row listened
+// to (mel_gat_attention_weights).  One wave per target row r, the forward's sources in the forward's order, edge_score as there.
+//   pass 1  the online (m, l) of the forward;
+//   pass 2  alpha = exp(e - m) * 1 / (l + 1e-16) - the expression of the backward's passes - stored by the first lane of each head:
+//           the `heads` floats of source j are adjacent, a.out + (r * n + j) * heads;
+//   zeros   every (j, h) with j NOT a source of r, a lane per element: the two sets of addresses are disjoint, so nothing is
+//           written twice, every element of the row's n * heads is written once and the caller never clears the buffer.
+// The zero fill is addressed by node and head, not by channel: idle lanes (LIVE < 64) take part in it; they store no coefficient
+// and load no row (gload_live).  A target without a source runs no pass and gets a row of zeros.  a.out = alpha here.
+template <int VPL, int KIND, int LIVE>
+__global__ __launch_bounds__(256) void gat_attention_weights_kernel(GradArgs a) {
+    constexpr int HC = LIVE * VPL;
+    const int lane = lane_id();
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.rows) return;
+    const int g0 = (r / a.n) * a.n;
+    GVec<VPL> att;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) att.v[i] = 0.f;
+    if (KIND == MEL_CONV_GATV2) att = gload_live<VPL, LIVE>(a.att + lane * VPL, lane);
+    const GVec<VPL> xr = gload_live<VPL, LIVE>(a.xr + (size_t)r * HC + lane * VPL, lane);
+    // (the forward's set for every adjacency of n nodes; a stray bit from n on - a caller's error - must not become a store
+    // outside the row)
+    const NodeSet<2> src = sources_of<KIND>(a, r) & ns_full<2>(a.n);
+    float m = -INFINITY, l = 0.f;
+    for (NodeSet<2> s = src; ns_any(s); ns_clear_lowest(s)) {
+        const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + (size_t)(g0 + ns_lowest(s)) * HC + lane * VPL, lane);
+        const float e = edge_score<VPL, KIND>(a, xr, xl, att);
+        const float mn = fmaxf(m, e);
+        l = l * expf(m - mn) + expf(e - mn);
+        m = mn;
+    }
+    const float inv = 1.f / (l + 1e-16f);
+    float* row = a.out + (size_t)r * a.n * a.heads;                      // [n, heads]
+    const bool writes = lane % a.lanes_per_head == 0 && (LIVE == 64 || lane < LIVE);      // the first lane of a head
+    const int head = lane / a.lanes_per_head;
+    for (NodeSet<2> s = src; ns_any(s); ns_clear_lowest(s)) {
+        const int j = ns_lowest(s);
+        const GVec<VPL> xl = gload_live<VPL, LIVE>(a.xl + (size_t)(g0 + j) * HC + lane * VPL, lane);
+        const float alpha = expf(edge_score<VPL, KIND>(a, xr, xl, att) - m) * inv;
+        if (writes) row[j * a.heads + head] = alpha;
+    }
+    const int cells = a.n * a.heads;                                     // <= 128 * 64
+    for (int c = lane; c < cells; c += 64)
+        if (!ns_test(src, c / a.heads)) row[c] = 0.f;
+}
+
 // ---- global pool over the graph of (x * dm): hl_dgn.py:105-108 -------------------------------------------
 // one thread per (graph, channel); arg = node of the first maximum (max only)
 __global__ __launch_bounds__(256) void pool_forward_kernel(const float* __restrict__ x, const float* __restrict__ dm,
@@ -530,6 +577,27 @@ mel_status mel_gat_forward(const float* xl, const float* xv, const float* xr, co
     const int grid = (a.rows + 3) / 4;
     MEL_GRAD_DISPATCH(gat_full_forward_kernel, grid)
     return check_launch("mel_gat_forward");
+}
+
+mel_status mel_gat_attention_weights(const float* xl, const float* xr, const float* att, const uint64_t* adj, int64_t bs,
+                                     int32_t n, int32_t heads, int32_t channels, int32_t kind, float* alpha, void* stream) {
+    if (mel_status st = check_gat(xl, xr, adj, bs, n, heads, channels, kind, att, /* no values: */ xl)) return st;
+    if (!alpha) return fail(MEL_ERR_INVALID_ARG, "gat attention weights: alpha is null");
+    const int64_t cells = bs * n * n * heads;                   // (check_gat: bs * n <= 2^28, n <= 128, heads <= 64)
+    if (cells > (1ll << 31))
+        return fail(MEL_ERR_INVALID_ARG, "gat attention weights: bs * n * n * heads = %ld * %d * %d * %d = %lld elements > 2^31",
+                    (long)bs, n, n, heads, (long long)cells);
+    clear_stale_error();
+    GradArgs a{};
+    a.xl = xl, a.xv = xl, a.xr = xr, a.att = att, a.adj = adj;
+    const HeadLanes hl = head_lanes(heads, channels);
+    a.rows = (int)(bs * n), a.n = n, a.nw = set_words(n), a.lanes_per_head = hl.lanes_per_head, a.kind = kind;
+    a.scale = 1.0f / sqrtf((float)channels), a.heads = heads;
+    a.out = alpha;                                              // [rows, n, heads]
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = (a.rows + 3) / 4;
+    MEL_GRAD_DISPATCH(gat_attention_weights_kernel, grid)
+    return check_launch("mel_gat_attention_weights");
 }
 
 mel_status mel_gat_backward(const float* xl, const float* xv, const float* xr, const float* att, const uint64_t* adj,

@@ -2,6 +2,8 @@
 
 ``gat_attention``  relu(GATv2Conv / TransformerConv) given the dense projections, forward AND backward in HIP
                    (edge softmax + aggregation; l_dgn.py:125-126,133-134, hl_dgn.py:101-102, dgn_r.py:103-113);
+``gat_attention_weights`` / ``transformer_attention_weights``  the softmax coefficients of those two, [rows, n, heads], no
+                   gradient (``GraphQNetwork.attention_weights``);
 ``graph_pool``     (x * dm) -> global max / mean / add pool with its backward (hl_dgn.py:105-108);
 ``radius_graph``   the fp32 radius adjacency as uint64 source masks (networks/common.py:47-48), no gradient.
 
@@ -85,6 +87,30 @@ def gat_attention(xl, xr, att, bias, adj, n_nodes: int, heads: int, channels: in
 def transformer_attention(k, v, q, adj, n_nodes: int, heads: int, channels: int) -> torch.Tensor:
     """relu(TransformerConv(root_weight=False)) given key / value / query projections."""
     return _GatAttention.apply(k, v, q, None, None, adj, n_nodes, heads, channels, _lib.CONV_TRANSFORMER)
+
+
+def _attention_weights(xl, xr, att, adj, n_nodes: int, heads: int, channels: int, kind: int) -> torch.Tensor:
+    """alpha [rows, n, heads] of ``mel_gat_attention_weights``: detached, nothing recorded for autograd, every element written
+    by the kernel (``torch.empty``: no clearing launch)."""
+    xl, xr = xl.detach().contiguous(), xr.detach().contiguous()
+    att = att.detach().contiguous() if att is not None else None
+    rows = xl.shape[0]
+    alpha = torch.empty(rows, n_nodes, heads, dtype=torch.float32, device=xl.device)
+    _lib.check(_lib.load().mel_gat_attention_weights(xl.data_ptr(), xr.data_ptr(), att.data_ptr() if att is not None else None,
+                                                     adj.data_ptr(), rows // n_nodes, n_nodes, heads, channels, kind,
+                                                     alpha.data_ptr(), _stream(xl)), "mel_gat_attention_weights")
+    return alpha
+
+
+def gat_attention_weights(xl, xr, att, adj, n_nodes: int, heads: int, channels: int) -> torch.Tensor:
+    """The coefficients ``gat_attention`` aggregates with: alpha[r, j, h] of source node j (same graph) for target row r, the
+    self-loop included, 0 where j is not a source.  fp32 [rows, n, heads], no gradient."""
+    return _attention_weights(xl, xr, att, adj, n_nodes, heads, channels, _lib.CONV_GATV2)
+
+
+def transformer_attention_weights(k, q, adj, n_nodes: int, heads: int, channels: int) -> torch.Tensor:
+    """The coefficients of ``transformer_attention`` (no self-loop; a target without a source has a row of zeros)."""
+    return _attention_weights(k, q, None, adj, n_nodes, heads, channels, _lib.CONV_TRANSFORMER)
 
 
 class _GraphPool(torch.autograd.Function):

@@ -433,19 +433,37 @@ def radius_adjacency(pos: torch.Tensor) -> torch.Tensor:
     return within & ~eye
 
 
+def gatv2_alpha(att: torch.Tensor, x_l: torch.Tensor, x_r: torch.Tensor, adj: torch.Tensor) -> torch.Tensor:
+    """The softmax coefficients of GATv2Conv over the closed neighbourhood: ``att`` [H, C], ``x_l`` (sources) / ``x_r``
+    (targets) [bs, n, H, C], ``adj`` bool [bs, n, n] -> alpha [bs, i, j, H], exactly 0 where j is not a source of i."""
+    n = adj.shape[1]
+    mask = adj | torch.eye(n, dtype=torch.bool, device=adj.device)[None]
+    e = (F.leaky_relu(x_r[:, :, None] + x_l[:, None, :], 0.2) * att).sum(-1)             # [bs, i, j, H]
+    e = e.masked_fill(~mask[..., None], -float("inf"))
+    p = torch.exp(e - e.max(dim=2, keepdim=True).values)
+    p = torch.where(mask[..., None], p, torch.zeros((), device=p.device))
+    return p / (p.sum(dim=2, keepdim=True) + 1e-16)
+
+
 def gatv2_dense(conv: GATv2Conv, x: torch.Tensor, adj: torch.Tensor) -> torch.Tensor:
     bs, n, _ = adj.shape
     h, c = conv.heads, conv.out_channels
     x_l = conv.lin_l(x).view(bs, n, h, c)
     x_r = conv.lin_r(x).view(bs, n, h, c)
-    mask = adj | torch.eye(n, dtype=torch.bool, device=adj.device)[None]
-    e = (F.leaky_relu(x_r[:, :, None] + x_l[:, None, :], 0.2) * conv.att[0]).sum(-1)     # [bs, i, j, H]
-    e = e.masked_fill(~mask[..., None], -float("inf"))
-    p = torch.exp(e - e.max(dim=2, keepdim=True).values)
-    p = torch.where(mask[..., None], p, torch.zeros((), device=p.device))
-    alpha = p / (p.sum(dim=2, keepdim=True) + 1e-16)
+    alpha = gatv2_alpha(conv.att[0], x_l, x_r, adj)
     out = torch.einsum("bijh,bjhc->bihc", alpha, x_l)
     return out.reshape(bs * n, h * c) + conv.bias
+
+
+def transformer_alpha(k: torch.Tensor, q: torch.Tensor, adj: torch.Tensor) -> torch.Tensor:
+    """The softmax coefficients of TransformerConv over the open neighbourhood: ``k`` / ``q`` [bs, n, H, C], ``adj`` bool
+    [bs, n, n] -> alpha [bs, i, j, H]; a target without a source has a row of zeros."""
+    e = torch.einsum("bihc,bjhc->bijh", q, k) / math.sqrt(k.shape[-1])
+    e = e.masked_fill(~adj[..., None], -float("inf"))
+    e_max = e.max(dim=2, keepdim=True).values
+    e_max = torch.where(torch.isfinite(e_max), e_max, torch.zeros((), device=e.device))
+    p = torch.where(adj[..., None], torch.exp(e - e_max), torch.zeros((), device=e.device))
+    return p / (p.sum(dim=2, keepdim=True) + 1e-16)
 
 
 def transformer_dense(conv: TransformerConv, x: torch.Tensor, adj: torch.Tensor) -> torch.Tensor:
@@ -454,12 +472,7 @@ def transformer_dense(conv: TransformerConv, x: torch.Tensor, adj: torch.Tensor)
     q = conv.lin_query(x).view(bs, n, h, c)
     k = conv.lin_key(x).view(bs, n, h, c)
     v = conv.lin_value(x).view(bs, n, h, c)
-    e = torch.einsum("bihc,bjhc->bijh", q, k) / math.sqrt(c)
-    e = e.masked_fill(~adj[..., None], -float("inf"))
-    e_max = e.max(dim=2, keepdim=True).values
-    e_max = torch.where(torch.isfinite(e_max), e_max, torch.zeros((), device=e.device))
-    p = torch.where(adj[..., None], torch.exp(e - e_max), torch.zeros((), device=e.device))
-    alpha = p / (p.sum(dim=2, keepdim=True) + 1e-16)
+    alpha = transformer_alpha(k, q, adj)
     return torch.einsum("bijh,bjhc->bihc", alpha, v).reshape(bs * n, h * c)
 
 
@@ -522,6 +535,41 @@ def conv_relu(conv, x: torch.Tensor, adj, n: int, hip: bool) -> torch.Tensor:
     return F.relu(dense(conv, x, adj))
 
 
+def conv_attention_weights(conv, x: torch.Tensor, adj, n: int, hip: bool) -> torch.Tensor:
+    """The coefficients ``conv_relu(conv, x, adj, n, hip)`` aggregates with, alpha [bs, n (target), n (source), H], no gradient:
+    from ``mel_gat_attention_weights`` when hip (adj: uint64 masks), else from the dense formulation's own alpha."""
+    bs, h, c = x.shape[0] // n, conv.heads, conv.out_channels
+    tk = isinstance(conv, TransformerConv)
+    with torch.no_grad():
+        if hip:
+            from .autograd_ops import gat_attention_weights, transformer_attention_weights
+            if tk:
+                alpha = transformer_attention_weights(linear(conv.lin_key, x, hip), linear(conv.lin_query, x, hip), adj, n, h, c)
+            else:
+                alpha = gat_attention_weights(linear(conv.lin_l, x, hip), linear(conv.lin_r, x, hip), conv.att, adj, n, h, c)
+            return alpha.view(bs, n, n, h)
+        if tk:
+            return transformer_alpha(conv.lin_key(x).view(bs, n, h, c), conv.lin_query(x).view(bs, n, h, c), adj)
+        return gatv2_alpha(conv.att[0], conv.lin_l(x).view(bs, n, h, c), conv.lin_r(x).view(bs, n, h, c), adj)
+
+
+def dense_to_edges(alpha: torch.Tensor, adj: torch.Tensor, self_loops: bool):
+    """Dense coefficients -> upstream's ``return_attention_weights`` form, on the host.  ``alpha`` [bs, n, n, H] (target i,
+    source j), ``adj`` bool [bs, n, n] without self-loops -> (edge_index int64 [2, E], alpha [E, H]): row 0 the source and row 1
+    the target as global node ids ``b*n + i``, the edges of ``adj`` sorted by target, then by source; ``self_loops`` (GATv2Conv):
+    the ``bs*n`` loops (i, i) follow in node order, as ``add_self_loops`` leaves them."""
+    alpha, adj = alpha.detach().cpu(), adj.detach().cpu().bool()
+    bs, n = adj.shape[:2]
+    adj = adj & ~torch.eye(n, dtype=torch.bool)
+    b, i, j = adj.nonzero(as_tuple=True)                      # row-major: by graph, then target, then source
+    src, tgt, a = b * n + j, b * n + i, alpha[b, i, j]
+    if self_loops:
+        ids = torch.arange(bs * n)
+        src, tgt = torch.cat([src, ids]), torch.cat([tgt, ids])
+        a = torch.cat([a, alpha.diagonal(dim1=1, dim2=2).permute(0, 2, 1).reshape(bs * n, -1)])
+    return torch.stack([src, tgt]), a
+
+
 def unpack(obs: torch.Tensor, input_dim: int, n: int):
     bs = obs.shape[0]
     node = obs[:, :-1].reshape(bs, n, input_dim + 3).float()
@@ -568,6 +616,37 @@ class GraphQNetwork(HipForwardMixin, nn.Module):
     def forward(self, obs, state=None, info={}):
         logits = self._dispatch(self._prepare_obs(obs))
         return logits, (state if self._RETURNS_STATE else None)
+
+    def attention_weights(self, obs, layout: str = "dense") -> list:
+        """The attention coefficients of the convolutions on ``obs`` (what ``forward`` takes: ``[bs, 8N+1]``; the index column is
+        not read), one entry per convolution - ``conv1`` and, for the two-convolution networks, ``conv2`` on the decision-maker
+        masked rows - from the full-graph formulation of the learn path, without gradient: upstream's
+        ``conv(x, edge_index, return_attention_weights=True)``.
+
+        ``layout="dense"``: alpha fp32 ``[bs, n, n, heads]``, ``[b, i, j, h]`` = weight of source j for target i (GATv2Conv: the
+        self-loop on the diagonal), exactly 0 where j is not a source.  ``layout="edges"``: ``(edge_index int64 [2, E], alpha
+        [E, heads])`` on the host in upstream's form (:func:`dense_to_edges`).  On a ROCm device with ``learn_kernels == "hip"``
+        the coefficients come from ``mel_gat_attention_weights``, else from the dense torch formulation."""
+        if layout not in ("dense", "edges"):
+            raise ValueError(f"layout must be 'dense' or 'edges', got {layout!r}")
+        obs = self._prepare_obs(obs).to(self.device)
+        with torch.no_grad():
+            pos, feats, dm, _g = unpack(obs, self.input_dim, self.agents_num)
+            bs, n = pos.shape[:2]
+            hip = use_hip_autograd(self, obs)
+            adj = learn_adjacency(obs, pos, n, self.input_dim, hip)
+            x = mlp(self.encoder, feats.reshape(bs * n, -1), hip, final_relu=True)
+            convs, alphas = [self.conv1], [conv_attention_weights(self.conv1, x, adj, n, hip)]
+            if hasattr(self, "conv2"):
+                x = conv_relu(self.conv1, x, adj, n, hip) * dm.reshape(bs * n, 1)
+                convs.append(self.conv2)
+                alphas.append(conv_attention_weights(self.conv2, x, adj, n, hip))
+        if layout == "dense":
+            return alphas
+        if hip:                                         # the kernel's source-set words -> bool [bs, n, n] on the host
+            from ..env.episodes import sets_to_bool
+            adj = torch.from_numpy(sets_to_bool(adj.cpu().numpy(), n)).view(bs, n, n)
+        return [dense_to_edges(a, adj, self_loops=not isinstance(c, TransformerConv)) for c, a in zip(convs, alphas)]
 
     def torch_forward_all_agents(self, obs_matrix: torch.Tensor) -> torch.Tensor:
         """Q values of EVERY node of every graph as controlling agent: ``obs_matrix`` [G, 8N] (a round's shared observation,

@@ -1,7 +1,8 @@
 """``DGNRNetwork`` drop-in (reference: graph_env/env/utils/networks/dgn_r.py:13-129): encoder -> two
 ``TransformerConv(root_weight=False)`` layers with controlling-agent snapshots -> dueling head.  Same constructor, same
 state_dict keys (``conv{1,2}.lin_{key,query,value,skip}.*``), ``forward -> (logits, state)``; inference through
-mel_dgnr_forward."""
+mel_dgnr_forward.  ``attention_weights(obs)`` (GraphQNetwork) returns the coefficients of ``conv1`` and ``conv2`` (open
+neighbourhoods: a node without a neighbour has a row of zeros)."""
 from __future__ import annotations
 
 from .. import _lib

@@ -1,6 +1,7 @@
 """``HLDGNNetwork`` drop-in (reference: graph_env/env/utils/networks/hl_dgn.py:14-119): encoder ->
 one GATv2 layer -> decision-maker mask -> global max/mean/add pool -> dueling head.  Same constructor
-(``aggregator`` before ``dueling_param``), same state_dict keys, ``forward -> (logits, state)``."""
+(``aggregator`` before ``dueling_param``), same state_dict keys, ``forward -> (logits, state)``.
+``attention_weights(obs)`` (GraphQNetwork) returns the coefficients of its one convolution."""
 from __future__ import annotations
 
 import torch

@@ -3,6 +3,7 @@
 Same constructor signature, same parameter tree / state_dict keys (``encoder.model.{0,2}``, ``conv1.*``, ``conv2.*``,
 ``Q.model.{0,2,4}``, ``V.model.{0,2,4}`` or ``out_linear``), same ``forward(obs, state=None, info={}) -> (logits, None)``
 contract; the inference arithmetic runs in hand-written HIP through the C ABI (mel_ldgn_forward).
+``attention_weights(obs)`` (GraphQNetwork) returns the coefficients of ``conv1`` and ``conv2``, self-loops included.
 """
 from __future__ import annotations
 

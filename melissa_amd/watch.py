@@ -9,6 +9,10 @@ run test episodes on evaluation envs, report the episodes' statistics).
 the list out instead - env b plays positions ``b, b + E, ...``, each of the ``--episodes`` positions exactly once - drawn on
 the device and replayed from a HIP graph (:func:`melissa_amd.collect.evaluate_spread`).
 
+``--attention-out FILE [--attention-rounds K]`` also plays ``K`` greedy rounds on a small env batch of its own and writes what
+the policy saw, what it did and the convolutions' attention weights - which neighbours each node listened to - into an
+``.npz`` (:func:`record_attention`); the evaluation and its printed result are the same with and without it.
+
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
 ``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by ``python -m melissa_amd.train --epoch ...``
 (``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth``) or by the reference's trainer (keys ``model.*`` /
@@ -23,27 +27,63 @@ import json
 
 import torch
 
-from .collect import Collector, evaluate_spread
+from .collect import Collector, RoundLoop, evaluate_spread
 from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
 from .train import AGGREGATORS, N_DGN_NETWORK, build_network, check_network_args, load_policy_weights
 
 
+def record_attention(policy, venv, rounds: int, seed: int = 0) -> dict:
+    """Play ``rounds`` greedy rounds on ``venv`` with the eager round loop (:class:`melissa_amd.collect.RoundLoop`, one launch
+    sequence per round, no HIP graph) and keep, per round and env, what the policy saw and which neighbours it listened to:
+
+    ``obs`` fp32 [K, E, 8N]  the observation matrix the round's forward read;  ``acted`` bool [K, E, N]  the round's active
+    agents;  ``action`` int32 [K, E, N]  their actions (-1 for a node that did not act);  ``alpha_conv1`` (``alpha_conv2`` for
+    the two-convolution models) fp32 [K, E, N, N, H]  ``policy.model.attention_weights`` of ``obs``: target i, source j."""
+    net, n, E, dev = policy.model, venv.n, venv.env_num, venv.device
+    loop = RoundLoop(venv, policy, episodes_per_env=int(rounds) + 2, seed=seed, eps=0.0, use_graph=False)   # an episode per round at most
+    node = torch.arange(n, device=dev)
+    rec: dict = {"obs": [], "acted": [], "action": []}
+    with torch.no_grad():
+        for _ in range(int(rounds)):
+            obs = loop._obs_matrix[:, :8 * n].clone()
+            acted = ((loop.live.reshape(E, -1)[:, node // 64] >> (node % 64)) & 1).bool()          # [E, N]
+            loop.step()
+            action = torch.full((E, n), -1, dtype=torch.int32, device=dev)
+            if loop.per_env_logits:                        # dense layout: act[b * n + i]
+                action[acted] = loop.act.view(E, n)[acted]
+            else:                                          # rows by env, then by agent id: the order of the set bits
+                action[acted] = loop.act[:int(acted.sum())]
+            alphas = net.attention_weights(torch.cat([obs, obs.new_zeros(E, 1)], dim=1))
+            rec["obs"].append(obs), rec["acted"].append(acted), rec["action"].append(action)
+            for k, a in enumerate(alphas):
+                rec.setdefault(f"alpha_conv{k + 1}", []).append(a)
+    errors = loop.counters()["errors"]
+    if errors:
+        raise RuntimeError(f"env error flags {errors:#x} while recording attention weights")
+    return {k: torch.stack(v).cpu().numpy() for k, v in rec.items()}
+
+
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
           dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
           graphs=16, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
-          aggregator_function="max"):
+          aggregator_function="max", attention_out=None, attention_rounds=8):
     """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
     random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
     ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
     statistic, pooled on the device; ``n_info_rows`` steps) instead of over the episodes' final rows.  Not with ``spread``:
     the envs that finish their share early keep playing, and those surplus episodes would enter the pool.
     ``hidden_emb`` ... ``aggregator_function``: the network flags of :func:`melissa_amd.train.train`; ``load`` of a checkpoint
-    trained at another shape is a ValueError naming the mismatching key and both shapes."""
+    trained at another shape is a ValueError naming the mismatching key and both shapes.
+    ``attention_out``: path of an ``.npz`` that receives :func:`record_attention` of ``attention_rounds`` greedy rounds on a
+    separate batch of ``min(envs, 4)`` envs (every env walks the test list from the top, ``spread`` or not), played after the
+    evaluation: the returned dict is the same with and without it."""
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function,
                        feature_dtype=feature_dtype)
     if spread and collect_stats != "episodes":
         raise ValueError("collect_stats='steps' is not offered with spread: surplus episodes would enter the pool")
+    if attention_out is not None and int(attention_rounds) < 1:
+        raise ValueError(f"attention_rounds={attention_rounds}: at least one round")
     torch.manual_seed(seed)
     net = build_network(model, n_nodes, device, hidden=hidden_emb, heads=num_heads, dueling_q_hidden_sizes=dueling_q_hidden_sizes,
                         dueling_v_hidden_sizes=dueling_v_hidden_sizes, aggregator=aggregator_function)
@@ -67,6 +107,15 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64,
                         stats=collect_stats)
         out = col.collect(n_episode=episodes)
+    if attention_out is not None:
+        # AFTER the evaluation and on an env batch of its own (built like the evaluation's: same pool, seed and flags), so the
+        # result below is what it is without the flag
+        import numpy as np
+        side = HipGraphVectorEnv(min(envs, 4), n_nodes, graph_pool=pool, dynamic_graph=dynamic_graph, device=device, max_moves=64,
+                                 seed=seed, construct_like_reference=False, is_testing=True, num_test_episodes=episodes,
+                                 scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic)
+        with open(attention_out, "wb") as f:
+            np.savez(f, **record_attention(policy, side, attention_rounds, seed=seed))
     # the scalars of the collect result (counts, speed, mean return / length, mean of every logger_stats key) as a plain dict
     keys = ["n/ep", "n/st", "collect_time", "collect_speed"] + (["rew", "len"] if out.returns_stat is not None else []) \
         + list(out.info.stats) + (["n_info_rows"] if collect_stats == "steps" else [])
@@ -102,6 +151,11 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dueling-v-hidden-sizes", type=int, nargs="*", default=[128, 128])
     ap.add_argument("--aggregator-function", type=str, default="max", choices=list(AGGREGATORS),
                     help="graph pool of the HL-DGN models")
+    ap.add_argument("--attention-out", default=None, metavar="FILE",
+                    help=".npz that receives obs, acted, action and the convolutions' attention weights (alpha_conv1, "
+                         "alpha_conv2: [rounds, envs, N target, N source, heads]) of --attention-rounds greedy rounds on "
+                         "min(--envs, 4) envs of their own; the evaluation is unaffected")
+    ap.add_argument("--attention-rounds", type=int, default=8, help="rounds recorded into --attention-out")
     return ap
 
 
@@ -115,6 +169,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error(str(e))
     if a.spread and a.collect_stats != "episodes":
         ap.error("--collect-stats steps is not offered with --spread (surplus episodes would enter the pool)")
+    if a.attention_rounds < 1:
+        ap.error("--attention-rounds: at least one round")
     return a
 
 
@@ -128,7 +184,8 @@ def main(argv=None):
                            scripted_agents_ratio=a.scripted_agents_ratio, spread=a.spread, collect_stats=a.collect_stats,
                            graph_pool=a.graph_pool, graphs=a.graphs, hidden_emb=a.hidden_emb, num_heads=a.num_heads,
                            dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
-                           dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function)))
+                           dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
+                           attention_out=a.attention_out, attention_rounds=a.attention_rounds)))
 
 
 if __name__ == "__main__":
