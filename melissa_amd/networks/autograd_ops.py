@@ -198,6 +198,49 @@ def _transpose(src: torch.Tensor, pad_to: int = 1) -> torch.Tensor:
     return dst
 
 
+_REPLAY_SAFE_COLUMN_SUMS = False
+
+
+def set_replay_safe_column_sums(on: bool) -> None:
+    """How a bias gradient sums the rows of ``dy`` [M, N].  Off (the default): ``dy.sum(dim=0)``, as ever.  On: the rows of the
+    transposed copy, ``dy.t().contiguous().sum(dim=1)`` - one workgroup per column, nothing shared between workgroups.
+
+    torch's reduction over the slow dimension splits a column over several workgroups that meet through a staging buffer and a
+    counter, zeroed by a memset ahead of the launch.  Replayed from a HIP graph, such a sum has been seen to leave its output
+    unwritten from some replay on, depending on what else ran on the device between the replays (NOTES.md "Resuming a run"):
+    the update then takes a stale bias gradient, and two processes that should compute the same weights do not.  A run that
+    must be continued bit for bit (``train(save_state=...)`` / ``train(resume_state=...)``) therefore sums this way; the two
+    forms add in different orders, so their results differ in the last bits and every other run keeps the first."""
+    global _REPLAY_SAFE_COLUMN_SUMS
+    _REPLAY_SAFE_COLUMN_SUMS = bool(on)
+
+
+def replay_safe_column_sums() -> bool:
+    return _REPLAY_SAFE_COLUMN_SUMS
+
+
+def column_sum(dy: torch.Tensor) -> torch.Tensor:
+    """[M, N] -> [N]: the bias gradient of a linear layer (:func:`set_replay_safe_column_sums`)."""
+    if _REPLAY_SAFE_COLUMN_SUMS and dy.is_cuda:
+        return dy.t().contiguous().sum(dim=1)
+    return dy.sum(dim=0)
+
+
+class _AddBias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, bias):
+        return y + bias
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, column_sum(dy.contiguous())
+
+
+def add_bias(y: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """``y + bias`` for y [M, N], bias [N], whose bias gradient is :func:`column_sum`."""
+    return _AddBias.apply(y, bias)
+
+
 def hip_linear_supported(in_features: int, out_features: int) -> bool:
     """mel_gemm_f32 tiles 64 output columns by 32 contraction steps; forward needs K % 32 == 0 and N % 64 == 0, the two
     backward products additionally K % 64 == 0 (dX has K columns, dW too)."""
@@ -237,7 +280,7 @@ class _HipLinear(torch.autograd.Function):
             else:                                         # long batches: split-K over the rows (padded transposed copies)
                 dw = _weight_grad(dy, x, w)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy.sum(dim=0)
+            db = column_sum(dy)
         return dx, dw, db, None
 
 

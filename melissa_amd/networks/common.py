@@ -499,6 +499,10 @@ def linear(lin: nn.Linear, x: torch.Tensor, hip: bool, relu: bool = False) -> to
         from .autograd_ops import hip_linear, hip_linear_supported
         if hip_linear_supported(lin.in_features, lin.out_features):
             return hip_linear(x, lin.weight, lin.bias, relu)
+        from .autograd_ops import add_bias, replay_safe_column_sums
+        if replay_safe_column_sums() and lin.bias is not None and x.is_cuda:
+            y = add_bias(F.linear(x, lin.weight), lin.bias)    # (the bias gradient's column sum: see set_replay_safe_column_sums)
+            return F.relu(y) if relu else y
     return F.relu(lin(x)) if relu else lin(x)
 
 

@@ -140,6 +140,14 @@ class RoundReplay:
         return out
 
 
+    def sampler_scratch(self) -> None:
+        """The device sampler's draw counter (state: every sample advances it) and prefix scratch, created by the first sample -
+        or by whoever restores a saved counter before one (:mod:`melissa_amd.train_state`)."""
+        if not hasattr(self, "_draws"):
+            dev = self.obs.device
+            self._draws = torch.zeros(1, dtype=torch.int64, device=dev)            # device-side draw counter
+            self._prefix = torch.empty(self.B * self.K + 1, dtype=torch.int32, device=dev)
+
     def _device_batch(self, batch_size: int, n_step: int, gamma: float, generator):
         """Output tensors of a one-launch sample + what both samplers pass to the library: (out, MelReplayBatch, discount, seed)."""
         import ctypes as C
@@ -148,9 +156,7 @@ class RoundReplay:
             if int(self.cursor.max()) < 1:
                 raise ValueError("cannot sample from an empty replay: run the collect loop first")
             self._nonempty = True
-        if not hasattr(self, "_draws"):
-            self._draws = torch.zeros(1, dtype=torch.int64, device=dev)            # device-side draw counter
-            self._prefix = torch.empty(self.B * self.K + 1, dtype=torch.int32, device=dev)
+        self.sampler_scratch()
         width = 8 * self.n + 1
         out = dict(obs=torch.empty(batch_size, width, device=dev), boot_obs=torch.empty(batch_size, width, device=dev),
                    act=torch.empty(batch_size, dtype=torch.int64, device=dev), ret=torch.empty(batch_size, device=dev),

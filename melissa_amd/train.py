@@ -234,7 +234,7 @@ def replay_rounds_for(buffer_size: int, envs: int, n_nodes: int) -> int:
 
 
 def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, step_per_epoch, rank, world, device, best_path,
-                last_path, pace=None, pooled=None):
+                last_path, pace=None, pooled=None, state_io=None):
     """The reference's training structure ([3P] tianshou ``OffpolicyTrainer`` as l_dgn.py:246-261 configures it): evaluate, then
     ``epoch`` times [update iterations until ``step_per_epoch`` more env steps are collected; evaluate; keep the best policy], then
     save the last one.  env steps = decisions x ``world``, the decisions being this rank's - with several ranks the smallest
@@ -252,12 +252,23 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     derives the number from the same agreed count, so all take the same updates.  The target-network sync keeps counting
     updates.  Epoch records then also carry ``update_debt`` (0).
     ``pooled()`` (``--collect-stats steps``): the means of the ``logger_stats`` of every env step this rank's training envs played
-    since the last call; every epoch record carries them (``train_info_rows``, ``train_<key>``)."""
+    since the last call; every epoch record carries them (``train_info_rows``, ``train_<key>``).
+    ``state_io`` = (write, restore, stop_after), each optional (:mod:`melissa_amd.train_state`): ``write(numbers)`` is called with
+    this function's own numbers and records after every epoch's evaluation - after ``before_first_epoch()`` for epoch 0, so
+    that every state holds a captured update's two warm-up updates; ``restore()`` replaces the first evaluation: the update is
+    captured where a fresh run captures it, then ``restore()`` overwrites everything and hands back the numbers a ``write`` was
+    given, and the loop goes on with the epoch after ``state_epoch``; ``stop_after``: the last epoch this process runs."""
     import torch
     from . import parallel
+    write, restore, stop_after = state_io if state_io is not None else (None, None, None)
     if rank == 0:
         os.makedirs(os.path.dirname(best_path), exist_ok=True)
     epochs, best = [], None
+
+    def numbers(index):
+        return dict(state_epoch=index, env_step=env_step, base=base, updates=updates, iterations=iterations, seconds=seconds,
+                    epochs=epochs, best_epoch=None if best is None else best[0], best_rew=None if best is None else best[1],
+                    loss_first=None if first is None else float(first), loss_last=None if last is None else float(last))
 
     def test(index, env_step, **more):
         nonlocal best
@@ -275,13 +286,25 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
         epochs.append(rec)
         parallel.barrier()
 
-    env_step = base = _agreed_decisions(loop, world, device) * world
-    test(0, env_step, overshoot=0, updates=0, seconds=0.0, **({} if pace is None else {"update_debt": 0}))
-    before_first_epoch()
-    stale = _StaleDecisionCount(loop, world)
     first = last = None
-    updates, seconds, iterations = 0, 0.0, 0
-    for e in range(1, epoch + 1):
+    updates, seconds, iterations, start = 0, 0.0, 0, 1
+    if restore is None:
+        env_step = base = _agreed_decisions(loop, world, device) * world
+        test(0, env_step, overshoot=0, updates=0, seconds=0.0, **({} if pace is None else {"update_debt": 0}))
+        before_first_epoch()
+        if write is not None:
+            write(numbers(0))
+    else:
+        before_first_epoch()
+        run = restore()
+        env_step, base, updates, iterations, seconds = (run[k] for k in ("env_step", "base", "updates", "iterations", "seconds"))
+        first, last, start = run["loss_first"], run["loss_last"], int(run["state_epoch"]) + 1
+        epochs.extend(run["epochs"])
+        best = None if run["best_epoch"] is None else (run["best_epoch"], run["best_rew"])
+    # (a resumed run's counter starts empty like the fresh run's: its first push hands back nothing, where the straight
+    # run's first push of an epoch hands back the count the previous epoch ended on - below the target and already settled)
+    stale = _StaleDecisionCount(loop, world)
+    for e in range(start, epoch + 1):
         target = env_step + step_per_epoch
         n, t0, more = 0, time.perf_counter(), {}
         if pace is None:
@@ -317,6 +340,10 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
         dt = time.perf_counter() - t0
         updates, seconds = updates + n, seconds + dt
         test(e, env_step, overshoot=env_step - target, updates=n, seconds=dt, **more)
+        if write is not None:
+            write(numbers(e))
+        if stop_after is not None and e >= stop_after:
+            break
     if rank == 0:
         torch.save(policy.state_dict(), last_path)             # l_dgn.py:263-266
     parallel.barrier()
@@ -334,7 +361,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
           update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes", graph_pool=None,
           hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
-          aggregator_function="max"):
+          aggregator_function="max", save_state=False, stop_after_epoch=None, resume_state=None):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -376,7 +403,16 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     ``hidden_emb`` / ``num_heads`` / ``dueling_q_hidden_sizes`` / ``dueling_v_hidden_sizes`` / ``aggregator_function``: the
     reference's network flags (common.py:29-30,41-43) with its defaults; a shape the HIP path does not run is a ValueError with
     the reason before anything is built (:func:`check_network_args`); a run at another shape than the default 128 x 4 records
-    ``hidden_emb`` and ``num_heads`` in its result."""
+    ``hidden_emb`` and ``num_heads`` in its result.
+    ``save_state`` / ``stop_after_epoch`` / ``resume_state`` (epoch mode; :mod:`melissa_amd.train_state`, NOTES.md "Resuming a
+    run"): ``save_state`` writes this rank's FULL training state after every epoch's evaluation to
+    ``<logdir>/<model>/weights/<model_name>_state.pth`` (``_state.rank<r>.pth`` with several ranks; the result carries
+    ``state_path``); ``stop_after_epoch=K`` ends the process after epoch K of the ``epoch`` the run has in all (``epoch`` stays
+    the total: the eps horizon depends on it); ``resume_state=FILE`` continues the run that wrote FILE from the epoch after
+    the one it holds, bit for bit what the uninterrupted run computes.  The file's header must be this call's: a ValueError
+    names the first argument that differs, before anything is built."""
+    from . import train_state
+    train_state.check_resume_args(epoch, save_state, stop_after_epoch, resume_state, resume_path)
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function)
     if collect_stats not in ("episodes", "steps"):
         raise ValueError(f"collect_stats={collect_stats!r}: 'episodes' or 'steps'")
@@ -398,9 +434,42 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     from .replay import PrioritizedRoundReplay, RoundReplay
     if backend != "gloo":
         launch.check_rank_device()                             # exit 2 when LOCAL_RANK names a GPU this rank cannot see
+    # a run that is to be continued bit for bit sums its bias gradients in the form a graph replay cannot disturb; every other
+    # run keeps the form it has always had, and with it its weights (networks/autograd_ops.py: set_replay_safe_column_sums)
+    from .networks.autograd_ops import set_replay_safe_column_sums
+    set_replay_safe_column_sums(bool(save_state) or resume_state is not None)
     rank, local_rank, world = parallel.init_distributed(backend)
     device = torch.device("cuda", local_rank if backend != "gloo" else 0)
     torch.cuda.set_device(device)
+    paced = update_per_step is not None
+    if buffer_size is not None:
+        replay_rounds = replay_rounds_for(buffer_size, envs, n_nodes)
+    if paced:
+        rounds_per_update = rounds_per_collect(step_per_collect, envs, world)
+    if capture_updates is None:
+        # on by default, with any number of ranks: the collective stays EAGER between two graphs (pack | all-reduce | unpack +
+        # step), so RCCL never enters a capture; rehearsed with two ranks on one GPU (tests/test_gpu_round.py)
+        capture_updates = probe is None
+    captured = bool(capture_updates) and device.type == "cuda"
+    header = saved = None
+    if save_state or resume_state is not None:
+        from . import _lib
+        header = train_state.state_header(
+            model=model, n_nodes=n_nodes, envs=envs, world=world, rank=rank, hidden_emb=hidden_emb, num_heads=num_heads,
+            dueling_q_hidden_sizes=dueling_q_hidden_sizes, dueling_v_hidden_sizes=dueling_v_hidden_sizes,
+            aggregator_function=aggregator_function, batch_size=batch_size, n_step=n_step, gamma=gamma, lr=lr,
+            target_update_freq=target_update_freq, prio_buffer=bool(prio_buffer), alpha=alpha, beta=beta, heuristic=heuristic,
+            scripted_agents_ratio=scripted_agents_ratio, epoch=int(epoch), step_per_epoch=int(step_per_epoch),
+            eps_train=eps_train, eps_train_final=eps_train_final, exploration_fraction=exploration_fraction,
+            update_per_step=None if update_per_step is None else float(update_per_step), step_per_collect=int(step_per_collect),
+            replay_rounds=int(replay_rounds), rounds_per_update=int(rounds_per_update), ring=int(ring), seed=int(seed),
+            captured=captured, collect_stats=collect_stats, mel_version=_lib.load().mel_version().decode())
+    if resume_state is not None:
+        # the header is compared before the network, the envs or a graph exist (the file is memory-mapped: reading the header
+        # reads no tensor); the training pool's identity follows as soon as there is a pool
+        resume_state = train_state.rank_state_path(resume_state, rank, world)
+        saved = train_state.load_state_file(resume_state)
+        train_state.check_state_header(saved["config"], header, resume_state)
     torch.manual_seed(seed)                                    # same init everywhere, then broadcast anyway
     net = build_network(model, n_nodes, device, hidden=hidden_emb, heads=num_heads,
                         dueling_q_hidden_sizes=dueling_q_hidden_sizes, dueling_v_hidden_sizes=dueling_v_hidden_sizes,
@@ -423,6 +492,10 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         graph_list = cached_graph_pool(n_nodes, graphs, 0, device=device)
     else:
         graph_list = connected_graph_pool(n_nodes, graphs, first_seed=0, device=device)
+    if header is not None:
+        header.update(train_state.pool_identity(graph_list))
+        if saved is not None:
+            train_state.check_state_header(saved["config"], header, resume_state)
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=graph_list, dynamic_graph=True, device=device, max_moves=48,
                              seed=1000 + rank * envs, construct_like_reference=False, heuristic=heuristic,
                              scripted_agents_ratio=scripted_agents_ratio)
@@ -433,11 +506,6 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         def pooled():
             count, stats = venv.read_step_stats(reset=True)
             return dict(train_info_rows=count, **{f"train_{k}": v.mean for k, v in stats.items()})
-    paced = update_per_step is not None
-    if buffer_size is not None:
-        replay_rounds = replay_rounds_for(buffer_size, envs, n_nodes)
-    if paced:
-        rounds_per_update = rounds_per_collect(step_per_collect, envs, world)
     if prio_buffer:
         replay = PrioritizedRoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours, alpha=alpha, beta=beta)
     else:
@@ -456,11 +524,6 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                          grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank, **({"fused_td": True} if paced else {}))
     with torch.no_grad():
         loop.run(max(n_step + 1, 8))                           # pre-fill (l_dgn.py:201)
-    if capture_updates is None:
-        # on by default, with any number of ranks: the collective stays EAGER between two graphs (pack | all-reduce | unpack +
-        # step), so RCCL never enters a capture; rehearsed with two ranks on one GPU (tests/test_gpu_round.py)
-        capture_updates = probe is None
-    captured = bool(capture_updates) and device.type == "cuda"
     warmup_updates = 2 if captured else 0
 
     def capture():
@@ -510,12 +573,31 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         name = model_name if model_name is not None else default_model_name()
         # (epoch mode captures the update AFTER the first evaluation: `param_checksum_start`, that evaluation and the first
         # _best.pth are all of the policy no update has touched)
+        state_path = train_state.rank_state_path(os.path.join(weights_dir, f"{name}_state.pth"), rank, world)
+
+        def write_state(numbers):
+            os.makedirs(weights_dir, exist_ok=True)
+            config = dict(header, state_epoch=numbers["state_epoch"])
+            numbers = dict(numbers, param_checksum_start=checksum_start)
+            train_state.write_state_file(train_state.gather_state(config, numbers, policy, learner, replay, loop, venv, device),
+                                         state_path)
+
+        def restore_state():
+            nonlocal checksum_start
+            numbers = train_state.restore_state(saved, policy, learner, replay, loop, venv, device)
+            checksum_start = numbers["param_checksum_start"]
+            return numbers
+
+        state_io = (write_state if save_state else None, restore_state if saved is not None else None,
+                    None if stop_after_epoch is None else int(stop_after_epoch))
         losses, dt, updates, extra = _run_epochs(loop, policy, iteration, evaluate, capture, int(epoch), int(step_per_epoch), rank,
                                                  world, device, os.path.join(weights_dir, f"{name}_best.pth"),
                                                  os.path.join(weights_dir, f"{name}_last.pth"),
                                                  pace=(collect, update, float(update_per_step)) if paced else None,
-                                                 pooled=pooled)
+                                                 pooled=pooled, state_io=state_io)
         extra["param_checksum_start"] = checksum_start
+        if save_state:
+            extra["state_path"] = state_path
         if paced:
             extra.update(update_per_step=float(update_per_step), rounds_per_collect=rounds_per_update,
                          replay_rounds=replay.K, fused_td=learner.fused_td)
@@ -543,6 +625,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     if rank == 0:
         log(json.dumps(out))
     parallel.barrier()
+    set_replay_safe_column_sums(False)
     return out
 
 
@@ -598,6 +681,14 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--logdir", type=str, default="log")
     ap.add_argument("--model-name", type=str, default=default_model_name())
     ap.add_argument("--resume-path", type=str, default=None)
+    # a run cut at epoch boundaries (needs --epoch, which stays the run's total)
+    ap.add_argument("--save-state", action="store_true", default=False,
+                    help="write the full training state after every epoch (<logdir>/<model>/weights/<model-name>_state.pth)")
+    ap.add_argument("--stop-after-epoch", type=int, default=None, metavar="K",
+                    help="end the process after epoch K of the --epoch the run has in all")
+    ap.add_argument("--resume-state", type=str, default=None, metavar="FILE",
+                    help="continue the run that wrote FILE (--save-state) from the epoch after the one it holds; every other "
+                         "argument must be that run's")
     # the reference's network flags, names and defaults (common.py:29-30,41-43)
     ap.add_argument("--hidden-emb", type=int, default=128, help="encoder width and channels per attention head")
     ap.add_argument("--num-heads", type=int, default=4, help="attention heads (a power of two, or 6)")
@@ -626,7 +717,8 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 update_per_step=a.update_per_step, step_per_collect=a.step_per_collect, buffer_size=a.buffer_size,
                 test_envs=a.test_envs, collect_stats=a.collect_stats, graph_pool=a.graph_pool,
                 hidden_emb=a.hidden_emb, num_heads=a.num_heads, dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
-                dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function)
+                dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
+                save_state=a.save_state, stop_after_epoch=a.stop_after_epoch, resume_state=a.resume_state)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -641,6 +733,11 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error(str(e))
     if a.update_per_step is not None and a.epoch is None:
         ap.error("--update-per-step paces the updates of the epoch mode: it needs --epoch")
+    from . import train_state
+    try:
+        train_state.check_resume_args(a.epoch, a.save_state, a.stop_after_epoch, a.resume_state, a.resume_path)
+    except ValueError as e:
+        ap.error(str(e))
     import sys
     given = sys.argv[1:] if argv is None else argv
     if a.graph_pool is not None and any(x == "--graphs" or x.startswith("--graphs=") for x in given):
@@ -656,7 +753,11 @@ def main(argv=None):
     rc = launch.maybe_spawn("-m", ["melissa_amd.train", *given], a.gpus, check_devices=a.backend != "gloo")
     if rc is not None:
         raise SystemExit(rc)
-    train(**train_kwargs(a))
+    from .train_state import StateMismatch
+    try:
+        train(**train_kwargs(a))
+    except StateMismatch as e:                                 # the state file is another run's: an argument error
+        arg_parser().error(str(e))
 
 
 if __name__ == "__main__":
