@@ -607,7 +607,7 @@ typedef struct mel_episode_stream {
     int32_t*  produced;        /* [B]    device: episodes drawn into the ring so far (= mel_episode_pool.produced) */
     uint32_t* draw_seed;       /* [B, K] device scratch: episode_seed per slot (core.py:372)                    */
     int32_t*  draw_graph;      /* [B, K] device scratch: graph index per slot (core.py:378)                     */
-    int32_t*  work;            /* [1 + 2*B*K] device scratch: work-item count, then (pool slot, unused) pairs   */
+    int32_t*  work;            /* [1 + 2*B*K] device scratch: work-item count, B*K pool slots, B*K movement seeds */
     int32_t*  new_count;       /* [B]    device scratch                                                         */
     int32_t   n_scripted;      /* scripted agents per episode: int(round(scripted_agents_ratio * N)) computed by the HOST
                                 * (Python's rounding, core.py:200); 0 = none, nothing more is drawn                      */
@@ -621,6 +621,13 @@ typedef struct mel_episode_stream {
     int32_t   reserved2;
     const uint32_t* test_seeds;/* [T] device: the seed list (mel_episode_test_seeds)                                      */
     int32_t*  test_discarded;  /* [B] device, zero at start: episodes discarded so far (they shift the walk)              */
+    uint32_t* key_scratch;     /* [2, key_capacity, 624] device scratch: the MT19937 keys of RandomState(episode_seed) and
+                                * RandomState(movement_seed) for the first key_capacity new episodes of a refill, seeded one
+                                * lane per episode; NULL with key_capacity 0                                              */
+    int32_t   key_capacity;    /* new episodes per refill whose keys fit; the ones beyond it seed inside their own
+                                * wavefront (same results, a longer refill).  A steady refill draws about refill_every *
+                                * B * (finished episodes per env and step), the first one B * (K - 1)                     */
+    int32_t   reserved3;
 } mel_episode_stream;
 
 /* For every env b draw episodes produced[b], produced[b]+1, ... while the slot they go to is free - i.e. up to episode

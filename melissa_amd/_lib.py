@@ -143,7 +143,8 @@ class MelEpisodeStream(C.Structure):
                 ("new_count", C.c_void_p), ("n_scripted", C.c_int32), ("reserved", C.c_int32),
                 ("draw_scripted", C.c_void_p), ("n_test", C.c_int32), ("test_env_step", C.c_int32),
                 ("test_episode_step", C.c_int32), ("reserved2", C.c_int32), ("test_seeds", C.c_void_p),
-                ("test_discarded", C.c_void_p)]
+                ("test_discarded", C.c_void_p), ("key_scratch", C.c_void_p), ("key_capacity", C.c_int32),
+                ("reserved3", C.c_int32)]
 
 
 ENV_ERR_MOVES_EXHAUSTED, ENV_ERR_NO_SELECTION, ENV_ERR_UNCOVERED_AGENT, ENV_ERR_EPISODE_UNDERRUN = 1, 2, 4, 8

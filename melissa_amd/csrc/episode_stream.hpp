@@ -1,17 +1,25 @@
 // Continuous episode supply: World.reset's sampling (graph_env/env/utils/core.py:343-395) on the device, bit for bit.
 //
-// Included by env.hip inside namespace mel (it calls env_reset / env_store).  Three launches per refill:
+// Included by env.hip inside namespace mel (it calls env_reset / env_store).  The launches of one refill, in stream order:
 //   episode_draw_kernel    one thread per env: the env's own generator (numpy Generator(PCG64)) draws episode_seed, the
 //                          graph and the scripted set for each free ring slot, in order        core.py:372,378,395
 //                          (evaluation schedule, n_test > 0: the seed is read from the fixed list at the episode's list
 //                          position and only the scripted set comes from the generator        core.py:351-352,395)
+//   episode_keys_kernel    one LANE per new episode, for the first key_capacity of them: init_genrand of
+//                          RandomState(episode_seed), that generator's first accepted randint(0, 1e9) = the movement seed
+//                          (after the graph draw under the evaluation schedule), init_genrand of RandomState(movement_seed);
+//                          both 624-word keys go to the stream's key scratch in HBM
 //   episode_fill_kernel    one wavefront per new episode: RandomState(episode_seed) (MT19937) draws movement seed, source,
 //                          interest density and the interested set (evaluation schedule: the graph first, and the density
-//                          from the list position instead of a draw, core.py:357-366); RandomState(movement_seed) fills the
-//                          movement offsets;
-//                          the graph is copied from the packed dataset; the scripted set loses the source (:213-215);
-//                          GraphEnv.reset + World.reset run into the snapshot batch    core.py:381-394,316-319,398-437
+//                          from the list position instead of a draw, core.py:357-366);
+//                          the graph is copied from the packed dataset; the scripted set loses the source (:213-215)
+//   episode_moves_kernel   four wavefronts per new episode (moving graphs only): RandomState(movement_seed) fills the
+//                          movement offsets                                                    core.py:316-319
+//   episode_snapshot_kernel one wavefront per new episode: GraphEnv.reset + World.reset run into the snapshot batch
+//                          core.py:398-437 - the only launch that holds an Env<W> in registers
 //   episode_publish_kernel produced[b] += new_count[b]
+// A work item past key_capacity (or one whose movement seed the keys launch did not reach within MEL_KEY_DRAWS outputs) seeds
+// its generators inside its own wavefront, on the scalar unit (mt_seed below).
 //
 // numpy algorithms restated here (numpy/random/src: pcg64.h, mt19937.c, distributions.c, legacy):
 //   PCG64       state' = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128); out = rotr64(hi ^ lo, hi >> 58)
@@ -252,30 +260,164 @@ __device__ __forceinline__ uint32_t mt_masked(Mt& m, uint32_t rng, int lane) {
     return v;
 }
 
-// One wavefront (a 64-thread workgroup) per new episode.
+// The first MEL_HEAD_DRAWS outputs of a freshly seeded generator (m.pos == 624: no regeneration yet), tempered, lane l of t0
+// holding output l and of t1 output 64 + l.  The first regeneration makes word k < 227 from the seeded words k, k + 1 and
+// k + 397 alone, so the head is computed without writing the key and without a barrier, and a draw from it is a v_readlane
+// with a scalar compare behind it instead of an LDS round trip per output.  A generator that is asked for more (every episode
+// of 100 nodes is, hardly one of 50) regenerates for real and goes on from LDS.
+constexpr int MEL_HEAD_DRAWS = 128;
+struct MtHead {
+    uint32_t t0, t1;
+    int drawn;          // wave-uniform
+};
+__device__ __forceinline__ MtHead mt_head(const Mt& m, int lane) {
+    MtHead h;
+    h.t0 = mt_temper(mt_twist(m.key[lane], m.key[lane + 1], m.key[lane + 397]));
+    h.t1 = mt_temper(mt_twist(m.key[64 + lane], m.key[65 + lane], m.key[461 + lane]));
+    h.drawn = 0;
+    return h;
+}
+__device__ __forceinline__ uint32_t mt_next32(Mt& m, MtHead& h, int lane) {
+    if (h.drawn < MEL_HEAD_DRAWS) {
+        const int p = h.drawn;
+        h.drawn = p + 1;
+        return (uint32_t)__builtin_amdgcn_readlane((int)(p < 64 ? h.t0 : h.t1), p & 63);
+    }
+    if (m.pos == 624 && h.drawn == MEL_HEAD_DRAWS) {        // the head is used up: outputs 128 .. 623 of this key come from LDS
+        mt_regen(m, lane);
+        m.pos = MEL_HEAD_DRAWS;
+        h.drawn = MEL_HEAD_DRAWS + 1;
+    }
+    return mt_next32(m, lane);
+}
+__device__ __forceinline__ uint32_t mt_masked(Mt& m, MtHead& h, uint32_t rng, int lane) {
+    if (rng == 0) return 0;
+    uint32_t mask = rng;
+    mask |= mask >> 1, mask |= mask >> 2, mask |= mask >> 4, mask |= mask >> 8, mask |= mask >> 16;
+    uint32_t v;
+    do {
+        v = mt_next32(m, h, lane) & mask;
+    } while (v > rng);
+    return v;
+}
+static_assert(MEL_HEAD_DRAWS == 128, "mt_next32 selects between two head registers");
+
+// ---- init_genrand for 64 generators at once, one lane each ---------------------------------------------------------
+// The recurrence cannot be split across words, but 64 of them run side by side: four vector instructions per word for 64
+// keys, against nine scalar + vector ones per word for the single key of mt_seed.  `out` is the workgroup's block of the key
+// scratch, [cnt <= 64][624] words, key-major, so that the wave which later owns a key reads it with coalesced loads: every 32
+// words of the 64 keys pass through an LDS tile (row stride 33 words: both the lane-per-key writes and the lane-per-word reads
+// are conflict free; 8 448 bytes, which fit beside a resident conv2 GEMM workgroup) and leave as 128-byte rows, two keys per
+// store instruction.
+__device__ __forceinline__ void mt_seed_lanes(uint32_t s, uint32_t* out, int cnt, uint32_t* tile, int lane) {
+    const int half = lane >> 5, col = lane & 31;
+    for (int c = 0; c < 624; c += 32) {
+        const int len = 624 - c < 32 ? 624 - c : 32;         // 19 chunks of 32 words and one of 16
+#pragma unroll 16
+        for (int j = 0; j < len; ++j) {
+            tile[lane * 33 + j] = s;
+            s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)(c + j + 1);
+        }
+        __syncthreads();
+        // (one row pair per trip.  Eight LDS reads in flight ahead of eight predicated stores measured WORSE on the headline:
+        // the keys launch 103 us against 65, and conv2's GEMM beside it 58 us against 46 - NOTES.md)
+        if (col < len)
+            for (int r = half; r < cnt; r += 2) out[(size_t)r * 624 + c + col] = tile[r * 33 + col];
+        __syncthreads();
+    }
+}
+
+// What the keys launch leaves in work[] for item w (behind the B*K slot entries): the movement seed (< 2^30), or this mark -
+// the item's wavefronts then seed in-wave and episode_fill_kernel stores the seed it draws, with the mark kept.
+constexpr uint32_t MEL_SEED_IN_WAVE = 0x80000000u;
+// Outputs of the episode generator the keys launch looks at per episode (the graph draw's rejections included).  The first
+// regeneration gives output k from key words k, k + 1 and k + 397 alone, so this must stay below 227.
+#ifndef MEL_KEY_DRAWS
+#define MEL_KEY_DRAWS 8
+#endif
+static_assert(MEL_KEY_DRAWS >= 1 && MEL_KEY_DRAWS <= 226, "output k of the first regeneration reads key[k + 397]");
+
+// 64 new episodes per workgroup, one lane each.
+__global__ __launch_bounds__(64) void episode_keys_kernel(StreamArgs a) {
+    __shared__ uint32_t tile[64 * 33];
+    const int lane = threadIdx.x;
+    const int n_work = a.st.work[0];
+    const int n_keys = n_work < a.st.key_capacity ? n_work : a.st.key_capacity;
+    const int w0 = blockIdx.x * 64;
+    if (w0 >= n_keys) return;                                // (workgroup-uniform)
+    const int cnt = n_keys - w0 < 64 ? n_keys - w0 : 64;
+    const bool on = lane < cnt;
+    const int w = w0 + lane;
+    uint32_t* ep = a.st.key_scratch + (size_t)w0 * 624;
+    mt_seed_lanes(on ? a.st.draw_seed[a.st.work[1 + w]] : 0u, ep, cnt, tile, lane);                 // core.py:373
+    if (!a.env.dynamic_graph) return;                        // a static graph never seeds a movement generator
+    // (the barrier that ends mt_seed_lanes makes the workgroup's own stores to `ep` visible to its lanes)
+    uint32_t movement_seed = MEL_SEED_IN_WAVE;
+    if (on) {
+        const uint32_t* k = ep + (size_t)lane * 624;
+        int p = 0;
+        auto output = [&]() {
+            const uint32_t y = mt_temper(mt_twist(k[p], k[p + 1], k[p + 397]));
+            p += 1;
+            return y;
+        };
+        bool open = true;
+        const uint32_t graph_rng = (uint32_t)(a.graphs.n_graphs - 1);
+        if (a.st.n_test > 0 && graph_rng != 0) {             // core.py:357 - the evaluation schedule draws the graph first
+            uint32_t mask = graph_rng;
+            mask |= mask >> 1, mask |= mask >> 2, mask |= mask >> 4, mask |= mask >> 8, mask |= mask >> 16;
+            open = false;
+            while (!open && p < MEL_KEY_DRAWS) open = (output() & mask) <= graph_rng;
+        }
+        while (open && p < MEL_KEY_DRAWS) {                                                         // :381 / :361
+            const uint32_t v = output() & 0x3FFFFFFFu;
+            if (v <= 999999999u) {
+                movement_seed = v;
+                break;
+            }
+        }
+        reinterpret_cast<uint32_t*>(a.st.work)[1 + a.st.n_envs * a.st.ring + w] = movement_seed;
+    }
+    mt_seed_lanes(movement_seed, a.st.key_scratch + ((size_t)a.st.key_capacity + w0) * 624, cnt, tile, lane);   // :382
+}
+
+// A generator whose key the keys launch seeded: 624 coalesced words from the scratch into LDS.
+__device__ __forceinline__ void mt_load_key(Mt& m, const uint32_t* src, int tid, int threads) {
+    for (int i = tid; i < 624; i += threads) m.key[i] = src[i];
+    m.pos = 624;
+    __syncthreads();
+}
+
+// One wavefront (a 64-thread workgroup) per new episode: the episode generator's draws and the pool slot.
 template <int W>
 __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
     __shared__ uint32_t key[624];
     const int lane = threadIdx.x;
     const int n = a.pool.n_nodes;
     const int n_work = a.st.work[0];
+    uint32_t* seeds = reinterpret_cast<uint32_t*>(a.st.work) + 1 + a.st.n_envs * a.st.ring;
     for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
         const int slot = a.st.work[1 + w];
         Mt m{key, 624};
         // ---- ep_rng = RandomState(episode_seed)                                                    core.py:373
-        mt_seed(m, a.st.draw_seed[slot], lane);
+        if (w < a.st.key_capacity) mt_load_key(m, a.st.key_scratch + (size_t)w * 624, lane, 64);
+        else mt_seed(m, a.st.draw_seed[slot], lane);
+        MtHead hd = mt_head(m, lane);
         const int T = a.st.n_test;                           // wave-uniform: > 0 = the evaluation schedule
         int g = a.st.draw_graph[slot];                       // training: the graph; evaluation: the list position
         const int t = g;
-        if (T > 0) g = (int)mt_masked(m, (uint32_t)(a.graphs.n_graphs - 1), lane);                  // :357 (one graph: no draw)
-        const uint32_t movement_seed = mt_masked(m, 999999999u, lane);                              // :381 / :361
-        const int origin = (int)mt_masked(m, (uint32_t)(n - 1), lane);                              // :384 / :364
+        if (T > 0) g = (int)mt_masked(m, hd, (uint32_t)(a.graphs.n_graphs - 1), lane);                  // :357 (one graph: no draw)
+        const uint32_t movement_seed = mt_masked(m, hd, 999999999u, lane);                              // :381 / :361
+        // (a seed the keys launch did not supply goes to the moves launch from here, marked)
+        if (lane == 0 && a.env.dynamic_graph && (w >= a.st.key_capacity || seeds[w] == MEL_SEED_IN_WAVE))
+            seeds[w] = movement_seed | MEL_SEED_IN_WAVE;
+        const int origin = (int)mt_masked(m, hd, (uint32_t)(n - 1), lane);                              // :384 / :364
         double density = a.st.fixed_interest_density;
         if (T > 0) {                                         // :365-366 - the list index is read after it was bumped
             density = (double)(((t + 1) % T) % 10 + 1) / 10.0;
         } else if (!a.st.has_density) {                                                             // :385
-            const uint32_t d0 = mt_next32(m, lane);
-            const uint32_t d1 = mt_next32(m, lane);
+            const uint32_t d0 = mt_next32(m, hd, lane);
+            const uint32_t d1 = mt_next32(m, hd, lane);
             const double range = 1.0 - 0.1;
             density = 0.1 + range * mt_double(d0, d1);
         }
@@ -284,7 +426,7 @@ __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
         int arr[W];
         MEL_W_FOR(h) arr[h] = lane + 64 * h;
         for (int i = n - 1; i >= 1; --i) {
-            const int j = (int)mt_masked(m, (uint32_t)i, lane);
+            const int j = (int)mt_masked(m, hd, (uint32_t)i, lane);
             const int vi = node_i32<W>(arr, i), vj = node_i32<W>(arr, j);
             MEL_W_FOR(h) {
                 if (lane + 64 * h == i) arr[h] = vj;
@@ -310,30 +452,67 @@ __global__ __launch_bounds__(64) void episode_fill_kernel(StreamArgs a) {
                 ns_store<W>(const_cast<uint64_t*>(a.pool.scripted), slot, ns_load<W>(a.st.draw_scripted, slot) & ~ns_bit<W>(origin));
             else if (a.pool.scripted) ns_store<W>(const_cast<uint64_t*>(a.pool.scripted), slot, ns_zero<W>());      // scripted_agents_ratio == 0
         }
-        // ---- movement_np_random = RandomState(movement_seed): step * uniform(-1, 1), x's then y's per move   :316-319,382
-        if (a.env.dynamic_graph) {
-            __syncthreads();
-            mt_seed(m, movement_seed, lane);
-            const int total = a.pool.max_moves * 2 * n;                   // doubles; 312 per regeneration of the key
-            double* out = const_cast<double*>(a.pool.moves) + (size_t)slot * total;
-            for (int base = 0; base < total; base += 312) {
-                mt_regen(m, lane);
-                for (int t = lane; t < 312 && base + t < total; t += 64) {
-                    const double u = mt_double(mt_temper(key[2 * t]), mt_temper(key[2 * t + 1]));
-                    const double x = -1.0 + 2.0 * u;                      // random_uniform: low + range * u
-                    out[base + t] = 0.06 * x;                             // NODES_MOVEMENT_STEP * ... (constants.py:4)
-                }
+        __syncthreads();                                                  // key[] is reused by the next work item
+    }
+}
+
+// mt_regen for a workgroup of 256, out of place: the three phases are 227, 227 and 170 words wide, one pass each, and with the
+// new key in a buffer of its own a phase only has to wait for the new words it reads - three barriers instead of mt_regen's
+// seven.  The last word (old key[623], new key[0] and key[396]) rides in the third phase.
+__device__ __forceinline__ void mt_regen_wide(const uint32_t* old, uint32_t* key, int tid) {
+    if (tid < 227) key[tid] = mt_twist(old[tid], old[tid + 1], old[tid + 397]);
+    __syncthreads();
+    if (tid < 227) key[227 + tid] = mt_twist(old[227 + tid], old[228 + tid], key[tid]);
+    __syncthreads();
+    if (tid < 169) key[454 + tid] = mt_twist(old[454 + tid], old[455 + tid], key[227 + tid]);
+    if (tid == 169) key[623] = mt_twist(old[623], key[0], key[396]);
+    __syncthreads();
+}
+
+// movement_np_random = RandomState(movement_seed): step * uniform(-1, 1), x's then y's per move        core.py:316-319,382
+// Four wavefronts (a 256-thread workgroup) per new episode.
+__global__ __launch_bounds__(256) void episode_moves_kernel(StreamArgs a) {
+    __shared__ uint32_t keys[2][624];
+    const int tid = threadIdx.x;
+    const int n_work = a.st.work[0];
+    const uint32_t* seeds = reinterpret_cast<const uint32_t*>(a.st.work) + 1 + a.st.n_envs * a.st.ring;
+    const int total = a.pool.max_moves * 2 * a.pool.n_nodes;              // doubles; 312 per regeneration of the key
+    for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int slot = a.st.work[1 + w];
+        Mt m{keys[0], 624};
+        const uint32_t seed = seeds[w];
+        if (seed & MEL_SEED_IN_WAVE) mt_seed(m, seed & ~MEL_SEED_IN_WAVE, tid & 63);    // (each wave writes the same 624 words)
+        else mt_load_key(m, a.st.key_scratch + ((size_t)a.st.key_capacity + w) * 624, tid, 256);
+        double* out = const_cast<double*>(a.pool.moves) + (size_t)slot * total;
+        int cur = 0;
+        for (int base = 0; base < total; base += 312) {
+            mt_regen_wide(keys[cur], keys[cur ^ 1], tid);
+            cur ^= 1;
+            const uint32_t* key = keys[cur];
+            for (int t = tid; t < 312 && base + t < total; t += 256) {
+                const double u = mt_double(mt_temper(key[2 * t]), mt_temper(key[2 * t + 1]));
+                const double x = -1.0 + 2.0 * u;                          // random_uniform: low + range * u
+                out[base + t] = 0.06 * x;                                 // NODES_MOVEMENT_STEP * ... (constants.py:4)
             }
         }
-        __syncthreads();                                                  // the slot is complete and visible to this wave
-        // ---- GraphEnv.reset + World.reset for this episode into its snapshot                        core.py:398-437
+        __syncthreads();                                                  // key[] is reused by the next work item
+    }
+}
+
+// GraphEnv.reset + World.reset for every new episode into its snapshot                               core.py:398-437
+// One wavefront per new episode, after its pool slot is complete.
+template <int W>
+__global__ __launch_bounds__(64) void episode_snapshot_kernel(StreamArgs a) {
+    const int lane = threadIdx.x;
+    const int n_work = a.st.work[0];
+    for (int w = blockIdx.x; w < n_work; w += gridDim.x) {
+        const int slot = a.st.work[1 + w];
         Env<W> s{};
         s.skip = SKIP_NONE, s.sel = NONE;
         MEL_W_FOR(h) s.act[h] = NONE, s.cur_act[h] = NONE;
         env_reset(a.snap, a.pool, slot, s, slot, 0, lane);
         s.ep_cursor = 0;
         env_store(a.snap, slot, lane, s);
-        __syncthreads();                                                  // key[] is reused by the next work item
     }
 }
 
@@ -411,20 +590,27 @@ static mel_status launch_episode_refill(const mel_episode_stream* st, const mel_
         sn->has_local_ratio != env->has_local_ratio || !sn->pos || !sn->scalars)
         return fail(MEL_ERR_INVALID_ARG, "the ring pool needs a snapshot batch of n_envs * ring envs with the env's settings");
     if (max_new < 0 || discard < 0) return fail(MEL_ERR_INVALID_ARG, "max_new=%d discard=%d", max_new, discard);
+    if (st->key_capacity < 0 || (st->key_capacity > 0 && !st->key_scratch))
+        return fail(MEL_ERR_INVALID_ARG, "key_capacity=%d key_scratch=%p", st->key_capacity, (void*)st->key_scratch);
     clear_stale_error();
     StreamArgs a{};
     a.st = *st, a.graphs = *graphs, a.pool = *pool, a.env = *env, a.snap = *sn;
     a.max_new = max_new > K ? K : max_new, a.discard = discard;
     StageScope t(MEL_STAGE_ENV_RESET, stream);
     MEL_LAUNCH(episode_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a);
-    // the work-item count lives on the device: a fixed grid loops over it (surplus workgroups leave at once)
+    // the work-item count lives on the device: fixed grids cover or loop over it (surplus workgroups leave at once)
+    const long most = (long)B * a.max_new;
+    const long keys = most < st->key_capacity ? most : st->key_capacity;
+    if (keys > 0) MEL_LAUNCH(episode_keys_kernel, dim3((unsigned)((keys + 63) / 64)), dim3(64), 0, stream, a);
     const long expect = (long)B * (a.max_new < 4 ? a.max_new : 4);
 #ifdef MEL_FILL_GRID
-    const int grid = MEL_FILL_GRID;                  // tuning: fewer, longer-lived fill waves
+    const int grid = MEL_FILL_GRID;                  // tuning: fewer, longer-lived waves in the three per-episode launches
 #else
     const int grid = (int)(expect < 256 ? 256 : (expect > 4096 ? 4096 : expect));
 #endif
     with_words(env->n_nodes, [&](auto w) { MEL_LAUNCH(episode_fill_kernel<decltype(w)::value>, dim3(grid), dim3(64), 0, stream, a); });
+    if (env->dynamic_graph) MEL_LAUNCH(episode_moves_kernel, dim3(grid), dim3(256), 0, stream, a);
+    with_words(env->n_nodes, [&](auto w) { MEL_LAUNCH(episode_snapshot_kernel<decltype(w)::value>, dim3(grid), dim3(64), 0, stream, a); });
     MEL_LAUNCH(episode_publish_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, a);
     return check_launch("episode_refill");
 }

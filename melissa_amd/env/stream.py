@@ -100,7 +100,10 @@ class EpisodeStream:
     def _configure(self, s, venv):
         """Hook: further fields of the mel_episode_stream ``s`` before the first refill."""
 
-    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
+    KEY_CAPACITY = 4096                # new episodes per refill whose generators are seeded one lane each (2 * 2.5 KB apiece)
+
+    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None,
+                 key_capacity: int | None = None):
         self._require_supported(venv)
         if ring < 3:
             raise ValueError("ring must be >= 3")
@@ -149,6 +152,13 @@ class EpisodeStream:
         s.work, s.new_count = self.work.data_ptr(), self.new_count.data_ptr()
         s.n_scripted = self.n_scripted
         s.draw_scripted = self.draw_scripted.data_ptr() if self.n_scripted else None
+        # the refill's key scratch: sized for the first fill (ring - 1 episodes per env) up to KEY_CAPACITY - a steady refill
+        # of the headline draws about 1.4 K episodes; the ones beyond the capacity seed inside their own wavefront
+        cap = min(B * (K - 1), self.KEY_CAPACITY) if key_capacity is None else int(key_capacity)
+        if cap < 0:
+            raise ValueError(f"key_capacity {cap}")
+        self.key_scratch = torch.empty(2 * cap * 624, dtype=torch.int32, device=dev) if cap else None
+        s.key_scratch, s.key_capacity = (self.key_scratch.data_ptr() if cap else None), cap
         self._configure(s, venv)
         self.struct = s
         self.side = torch.cuda.Stream(device=dev)
@@ -237,11 +247,12 @@ class TestEpisodeStream(EpisodeStream):
     __test__ = False                   # (not a test class, whatever the name says to pytest)
     kind = "device test stream"
 
-    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None):
+    def __init__(self, venv, seed, ring: int = 16, discard: int = 0, period: int | None = None,
+                 key_capacity: int | None = None):
         if discard and venv._sampler_kw.get("test_env_step", 0):
             raise ValueError(f"discard={discard}: only the reference's walk over the list discards episodes, a spread list "
                              f"is played from its top")
-        super().__init__(venv, seed, ring=ring, discard=discard, period=period)
+        super().__init__(venv, seed, ring=ring, discard=discard, period=period, key_capacity=key_capacity)
 
     def _require_supported(self, venv):
         kw = venv._sampler_kw
