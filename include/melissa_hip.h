@@ -258,7 +258,10 @@ mel_status mel_hldgn_forward(const mel_weights* w, int32_t aggregator, const flo
 /* The dense projection used by every layer above, exposed for tests and tuning:
  *   Y[m, n] = act(sum_k A[m, k] * W[n, k] + bias[n]),  A [M, lda], W [N, K] (nn.Linear layout), Y [M, ldy],
  * all device fp32; K % 32 == 0, N % 64 == 0.  tile: MEL_TILE_AUTO, MEL_TILE_64, MEL_TILE_128, MEL_TILE_64_PERSISTENT or
- * MEL_TILE_64_RING. */
+ * MEL_TILE_64_RING (ldy % 4 == 0, K >= 64).
+ * lda % 4 == 0 and A 16-byte aligned, for every tile code: the kernels fetch A in 16-byte pieces from A + m * lda + 4 c (the ring
+ * kernel by LDS-DMA); any other lda is MEL_ERR_UNSUPPORTED.  A's columns [K, lda) and rows >= M are never read (a tile's rows
+ * beyond M are clamped to row M - 1), Y's columns [N, ldy) and rows >= M never written. */
 mel_status mel_gemm_f32(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
                         int64_t M, int32_t N, int32_t K, int32_t relu, int32_t tile, void* stream);
 
@@ -274,7 +277,8 @@ mel_status mel_gemm_f32_t(const float* A, int32_t lda, int32_t a_t, const float*
 /* The same product with the contraction cut into `ksplit` equal chunks that run as independent work items and are summed in
  * chunk order afterwards: for the learn path's weight gradients dW = dY^T X, a few dozen output tiles over a contraction as
  * long as the batch has rows (one tile per workgroup would leave most of the chip idle).  K / 32 must be a multiple of
- * ksplit with at least two 32-steps per chunk; parts: device scratch of ksplit * M * N floats. */
+ * ksplit with at least two 32-steps per chunk; parts: device scratch of ksplit * M * N floats.  lda % 4 == 0 (16-byte LDS-DMA of
+ * A) and ldy % 4 == 0 (16-byte row stores), else MEL_ERR_UNSUPPORTED. */
 mel_status mel_gemm_f32_splitk(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
                                int64_t M, int32_t N, int32_t K, int32_t relu, int32_t ksplit, float* parts,
                                int64_t parts_floats, void* stream);
@@ -286,7 +290,8 @@ mel_status mel_gemm_f32_splitk(const float* A, int32_t lda, const float* W, cons
  * ldy % 4 == 0, no split-K; bit-identical to MEL_TILE_128), + MEL_TILE_PLANES_READY = W's planes are already in scratch (an earlier
  * call with the same W: benchmarks; not with MEL_TILE_WIDE); ksplit > 1: the 128 x 128 kernel's split-K (K / 16 a multiple of
  * ksplit, >= 4 steps per chunk, ldy % 4 == 0).
- * K % 32 == 0, K >= 128, N % 64 == 0; scratch: device, >= round_up(6 N K, 256) + (ksplit > 1 ? 4 ksplit M N : 0)
+ * K % 32 == 0, K >= 128, N % 64 == 0, lda % 4 == 0 (every tile's kernel fetches A in 16-byte pieces; MEL_ERR_UNSUPPORTED
+ * otherwise); scratch: device, >= round_up(6 N K, 256) + (ksplit > 1 ? 4 ksplit M N : 0)
  * + (tile 3 ? 6 K M : 0) bytes. */
 mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const float* bias, float* Y, int32_t ldy,
                               int64_t M, int32_t N, int32_t K, int32_t relu, int32_t tile, int32_t ksplit, void* scratch,

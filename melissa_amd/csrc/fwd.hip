@@ -1046,6 +1046,8 @@ mel_status mel_gemm_f32(const float* A, int32_t lda, const float* W, const float
                         int64_t M, int32_t N, int32_t K, int32_t relu, int32_t tile, void* stream) {
     if (!A || !W || !Y || M < 0 || M > (1ll << 30) || lda < K || ldy < N)
         return fail(MEL_ERR_INVALID_ARG, "bad gemm arguments");
+    if (lda % 4)        // every tile code's kernel fetches A in 16-byte pieces from A + row * lda + 4 c (the ring kernel by LDS-DMA)
+        return fail(MEL_ERR_UNSUPPORTED, "gemm: lda %% 4 == 0 (lda=%d)", lda);
     clear_stale_error();
     GemmArgs g;
     g.A = A, g.lda = lda, g.W = W, g.bias = bias, g.Y = Y, g.ldy = ldy, g.M = (int)M, g.N = N, g.K = K, g.relu = relu;
@@ -1074,10 +1076,10 @@ mel_status mel_gemm_f32_splitk(const float* A, int32_t lda, const float* W, cons
                                void* stream) {
     if (!A || !W || !Y || !parts || M <= 0 || M > (1ll << 30) || lda < K || ldy < N)
         return fail(MEL_ERR_INVALID_ARG, "bad split-K gemm arguments");
-    if (ksplit < 2 || K % GEMM_BK || (K / GEMM_BK) % ksplit || (K / GEMM_BK) / ksplit < 2 || N % 64 || ldy % 4 ||
+    if (ksplit < 2 || K % GEMM_BK || (K / GEMM_BK) % ksplit || (K / GEMM_BK) / ksplit < 2 || N % 64 || lda % 4 || ldy % 4 ||
         parts_floats < (int64_t)ksplit * M * N)
         return fail(MEL_ERR_UNSUPPORTED, "split-K gemm: K / 32 = %d must split into %d chunks of >= 2 steps, N %% 64 == 0, "
-                                         "ldy %% 4 == 0, parts >= ksplit * M * N floats", K / GEMM_BK, ksplit);
+                                         "lda %% 4 == 0, ldy %% 4 == 0, parts >= ksplit * M * N floats", K / GEMM_BK, ksplit);
     clear_stale_error();
     GemmArgs g;
     g.A = A, g.lda = lda, g.W = W, g.bias = bias, g.Y = Y, g.ldy = ldy, g.M = (int)M, g.N = N, g.K = K, g.relu = relu;
@@ -1093,8 +1095,10 @@ mel_status mel_gemm_f32_split(const float* A, int32_t lda, const float* W, const
     const bool blocks = tile % MEL_TILE_PLANES_READY == MEL_TILE_WIDE;    // gemm_planes_kernel: A goes through bf16 planes in scratch as well
     const int64_t a_bytes = blocks ? M * K * 6 : 0;
     const int64_t need = plane_bytes + a_bytes + (ksplit > 1 ? (int64_t)ksplit * M * N * 4 : 0);
-    if (K % 32 || N % 64 || scratch_bytes < need)
-        return fail(MEL_ERR_UNSUPPORTED, "split-precision gemm: K %% 32 == 0, N %% 64 == 0, scratch >= %lld bytes", (long long)need);
+    // lda: both split kernels fetch A in 16-byte pieces (the 128 x 128 tile's planner falls back to the 64 x 64 kernel, which does too)
+    if (K % 32 || N % 64 || lda % 4 || scratch_bytes < need)
+        return fail(MEL_ERR_UNSUPPORTED, "split-precision gemm: K %% 32 == 0, N %% 64 == 0, lda %% 4 == 0, scratch >= %lld bytes",
+                    (long long)need);
     clear_stale_error();
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (blocks) {
