@@ -898,6 +898,96 @@ mel_status mel_env_round(mel_env_batch* env, const mel_episode_pool* pool, const
  * count gates the rest).  MEL_ERR_INVALID_ARG: env or out NULL, an unbound batch, step_stats == NULL. */
 mel_status mel_env_step_stats(const mel_env_batch* env, double* out, int32_t reset, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training curves accumulated ON THE DEVICE (what the reference's train_agent hands to [3P] tianshou's logger, l_dgn.py:203-213,
+ * 237-238,260: train/reward, train/length, train/episode, train/eps, update/loss about every 1000 env steps).  The round loop and
+ * the update replay from HIP graphs and nothing in them reads the device, so the curve is summed per INTERVAL of env steps by two
+ * capturable launches into a caller-owned ring of records, and the host reads the ring where it synchronises anyway (the epoch
+ * boundary).  All pointers of mel_train_log are DEVICE memory:
+ *   records      double [capacity][MEL_TRAIN_LOG_DOUBLES]  one record per ring slot, fields MEL_TL_*
+ *   interval_id  int64  [capacity]   the interval a slot currently holds, -1 = empty (start: all -1)
+ *   counters     int64  [4]          MEL_TLC_*: records overwritten before they were drained, episode rows the env's log dropped,
+ *                                    second rows of one env within one drain; [3] reserved (start: 0)
+ *   base         uint64 [1]          env_step of interval 0's start; UINT64_MAX = not armed
+ *   drained_upto int64  [1]          the first interval the host has NOT read yet (start: 0)
+ * base and drained_upto are device memory so that launches captured before the host sets them follow the values it sets later.
+ * decisions / stride / n_envs / scale: the env batch's decision counters exactly as mel_exploration_schedule takes them.
+ *
+ * Both launches compute env_step = scale * sum_b decisions[b * stride] (64-bit integer sum).  Not armed, or env_step < base:
+ * nothing is recorded and no counter moves.  Otherwise k = (env_step - base) / interval, slot = k % capacity; a slot that holds
+ * another interval is first cleared to the empty record (every field 0.0 except the MEL_TL_*_MIN field +inf, the *_MAX fields
+ * -inf and MEL_TL_EPS_LAST -1.0) and takes id k - and if the id it held was >= *drained_upto (not -1), counters[MEL_TLC_LOST_RECORDS]
+ * is incremented.  Every field is a double; sums run in stream order, so the same launches on the same inputs give the same bits.
+ * Maxima and minima use explicit compares in which a NaN wins and stays (not fmax, see mel_td_target).
+ *
+ * mel_train_log_round - after every mel_env_round of a training loop.  Consumes rows [0, min(*env->log_cursor, log_capacity))
+ *   of the env batch's episode log (read only) and stores 0 to the cursor, armed or not.  Per interval: MEL_TL_EPISODES, the sum /
+ *   sum of squares / min / max of episode_rewards_sum, the sums of num_moves, coverage, coverage_interested_fraction and
+ *   total_messages_transmitted, MEL_TL_ROUNDS (+1 per call), MEL_TL_ENV_STEP_LAST and MEL_TL_EPS_LAST (*eps_dev; eps_dev NULL
+ *   leaves it).  Rows land in the episode log in atomic order; the record does not depend on it: rows are scattered by env id (in LDS),
+ *   lane t of one 256-lane workgroup folds envs t, t + 256, ... in ascending order and the lanes meet in a fixed pairwise tree
+ *   (lane t += lane t + o, o = 128, 64 .. 1).  Cursor values beyond log_capacity add to counters[MEL_TLC_LOST_EPISODES] (so do rows
+ *   whose env id is outside [0, n_envs)).  An env ends at most one episode per round; a second row of one env increments
+ *   counters[MEL_TLC_DUPLICATE_ENV_ROWS] and is still folded, the env's rows in (pool episode, row) order.  One launch.
+ * mel_train_log_update - once per update, directly in front of mel_adam_step, so that it sees the gradient Adam applies.
+ *   loss float [1], td float [batch] (mel_td_loss's), grads: the optimizer's table (grad[i], numel[i], i < count; numel >= 0).
+ *   Per interval: MEL_TL_UPDATES, sum / max / last of loss, sum and max of the update's mean_i |td_i| (lane l of one wavefront adds
+ *   |td_i| for i = l, l + 64, ... in double, lane 0 adds the lanes in order, / batch), max of |td_i|, sum / max / last of the global
+ *   gradient L2 norm.  The norm: every gradient widened to double and squared (exact); 256-lane workgroups sum chunks of
+ *   MEL_TRAIN_LOG_GRAD_CHUNK elements (lane t its elements t, t + 256, ..., then the pairwise tree above) into scratch, and the
+ *   one-wavefront launch that writes the record adds them (lane l a run of consecutive partials, lane 0 the lanes in order) and
+ *   takes the square root: no float atomics, relative error <= total_numel * 2^-52.  A NaN in loss, td or a gradient reaches the
+ *   record.  scratch: device, mel_train_log_scratch_bytes(grads) bytes (8 per chunk; 0 for a bad table).  Two launches.
+ * Neither reads on the host nor allocates: both replay from a HIP graph.
+ * MEL_ERR_INVALID_ARG: a null log / buffer / decisions / loss / td / grads, capacity < 1, interval < 1, n_envs < 1, stride < 1,
+ * batch outside [1, MEL_TD_MAX_BATCH], count outside [1, MEL_ADAM_MAX_TENSORS], a null gradient or negative numel, an env batch
+ * without an episode log (log_capacity < 1 or null log buffers) or with another n_envs; MEL_ERR_WORKSPACE: scratch_bytes too small. */
+#define MEL_TRAIN_LOG_DOUBLES     32
+#define MEL_TRAIN_LOG_GRAD_CHUNK  4096
+#define MEL_TL_EPISODES            0   /* episodes ended                                   empty 0      */
+#define MEL_TL_REW_SUM             1   /* sum of episode_rewards_sum                             0      */
+#define MEL_TL_REW_SQ              2   /* sum of its squares                                     0      */
+#define MEL_TL_REW_MIN             3   /*                                                        +inf   */
+#define MEL_TL_REW_MAX             4   /*                                                        -inf   */
+#define MEL_TL_MOVES_SUM           5   /* sum of num_moves                                       0      */
+#define MEL_TL_COVERAGE_SUM        6   /* sum of coverage                                        0      */
+#define MEL_TL_COV_INTERESTED_SUM  7   /* sum of coverage_interested_fraction                    0      */
+#define MEL_TL_MESSAGES_SUM        8   /* sum of total_messages_transmitted                      0      */
+#define MEL_TL_ROUNDS              9   /* round launches                                         0      */
+#define MEL_TL_ENV_STEP_LAST      10   /* env_step of the last launch of either kind             0      */
+#define MEL_TL_EPS_LAST           11   /* exploration rate of the last round                     -1     */
+#define MEL_TL_UPDATES            12   /* update launches                                        0      */
+#define MEL_TL_LOSS_SUM           13   /*                                                        0      */
+#define MEL_TL_LOSS_MAX           14   /*                                                        -inf   */
+#define MEL_TL_LOSS_LAST          15   /*                                                        0      */
+#define MEL_TL_TD_ABS_SUM         16   /* sum over updates of mean_i |td_i|                      0      */
+#define MEL_TL_TD_ABS_MEAN_MAX    17   /* max over updates of mean_i |td_i|                      -inf   */
+#define MEL_TL_TD_ABS_MAX         18   /* max over updates and samples of |td_i|                 -inf   */
+#define MEL_TL_GRAD_NORM_SUM      19   /*                                                        0      */
+#define MEL_TL_GRAD_NORM_MAX      20   /*                                                        -inf   */
+#define MEL_TL_GRAD_NORM_LAST     21   /*                                                        0      */
+                                       /* 22 .. 31: padding, 0                                          */
+#define MEL_TLC_LOST_RECORDS       0
+#define MEL_TLC_LOST_EPISODES      1
+#define MEL_TLC_DUPLICATE_ENV_ROWS 2
+typedef struct mel_train_log {
+    double*        records;
+    int64_t*       interval_id;
+    int64_t*       counters;
+    uint64_t*      base;
+    int64_t*       drained_upto;
+    const int32_t* decisions;
+    int64_t        interval;       /* env steps per record                                             */
+    int32_t        capacity;       /* ring slots                                                       */
+    int32_t        stride;
+    int32_t        n_envs;
+    uint32_t       scale;
+} mel_train_log;
+size_t     mel_train_log_scratch_bytes(const mel_adam_tensors* grads);
+mel_status mel_train_log_round(const mel_train_log* log, const mel_env_batch* env, const float* eps_dev, void* stream);
+mel_status mel_train_log_update(const mel_train_log* log, const float* loss, const float* td, int64_t batch,
+                                const mel_adam_tensors* grads, void* scratch, size_t scratch_bytes, void* stream);
+
 /* last() only (mutates is_new_round exactly like GraphEnv.observe, graph.py:205-211). */
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n,
                            const mel_env_obs* out, void* stream);
@@ -935,7 +1025,7 @@ const char* mel_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, for binding authors to check their mirrors
  * against: which = 0 mel_linear, 1 mel_gatv2, 2 mel_mlp, 3 mel_weights, 4 mel_select, 5 mel_env_batch,
  * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors,
- * 13 mel_replay_priority;
+ * 13 mel_replay_priority, 14 mel_train_log;
  * 0 for anything else. */
 size_t mel_abi_sizeof(int32_t which);
 const char* mel_version(void);

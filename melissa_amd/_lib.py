@@ -43,7 +43,8 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_select_action", "mel_env_state_bytes", "mel_env_bind", "mel_env_reset", "mel_env_step",
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
            "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
-           "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate")
+           "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate", "mel_train_log_scratch_bytes",
+           "mel_train_log_round", "mel_train_log_update")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -107,6 +108,21 @@ class MelAdamTensors(C.Structure):
                 ("grad", C.c_void_p * ADAM_MAX_TENSORS), ("exp_avg", C.c_void_p * ADAM_MAX_TENSORS),
                 ("exp_avg_sq", C.c_void_p * ADAM_MAX_TENSORS), ("step", C.c_void_p * ADAM_MAX_TENSORS),
                 ("numel", C.c_int64 * ADAM_MAX_TENSORS)]
+
+
+# mel_train_log: the record layout (MEL_TL_*), the counters (MEL_TLC_*) and the struct
+TRAIN_LOG_DOUBLES, TRAIN_LOG_GRAD_CHUNK = 32, 4096
+(TL_EPISODES, TL_REW_SUM, TL_REW_SQ, TL_REW_MIN, TL_REW_MAX, TL_MOVES_SUM, TL_COVERAGE_SUM, TL_COV_INTERESTED_SUM,
+ TL_MESSAGES_SUM, TL_ROUNDS, TL_ENV_STEP_LAST, TL_EPS_LAST, TL_UPDATES, TL_LOSS_SUM, TL_LOSS_MAX, TL_LOSS_LAST, TL_TD_ABS_SUM,
+ TL_TD_ABS_MEAN_MAX, TL_TD_ABS_MAX, TL_GRAD_NORM_SUM, TL_GRAD_NORM_MAX, TL_GRAD_NORM_LAST) = range(22)
+TLC_LOST_RECORDS, TLC_LOST_EPISODES, TLC_DUPLICATE_ENV_ROWS = 0, 1, 2
+TRAIN_LOG_NOT_ARMED = 2 ** 64 - 1         # *base while nothing is recorded
+
+
+class MelTrainLog(C.Structure):
+    _fields_ = [("records", C.c_void_p), ("interval_id", C.c_void_p), ("counters", C.c_void_p), ("base", C.c_void_p),
+                ("drained_upto", C.c_void_p), ("decisions", C.c_void_p), ("interval", C.c_int64), ("capacity", C.c_int32),
+                ("stride", C.c_int32), ("n_envs", C.c_int32), ("scale", C.c_uint32)]
 
 
 class MelEnvBatch(C.Structure):
@@ -274,6 +290,12 @@ def load(build_if_missing: bool = True):
     lib.mel_env_observe.argtypes = [E, vp, i64, O, vp]
     lib.mel_env_step_stats.restype = i32
     lib.mel_env_step_stats.argtypes = [E, vp, i32, vp]
+    lib.mel_train_log_scratch_bytes.restype = sz
+    lib.mel_train_log_scratch_bytes.argtypes = [C.POINTER(MelAdamTensors)]
+    lib.mel_train_log_round.restype = i32
+    lib.mel_train_log_round.argtypes = [C.POINTER(MelTrainLog), E, vp, vp]
+    lib.mel_train_log_update.restype = i32
+    lib.mel_train_log_update.argtypes = [C.POINTER(MelTrainLog), vp, vp, i64, C.POINTER(MelAdamTensors), vp, sz, vp]
     lib.mel_mpr_sets.restype = i32
     lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz

@@ -145,7 +145,8 @@ class RoundLoop:
     def __init__(self, venv: HipGraphVectorEnv, policy, episodes_per_env: int = 8, seed: int = 0,
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
                  stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: "bool | str | None" = None,
-                 ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None):
+                 ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None,
+                 train_log=None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
         ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes;
@@ -153,8 +154,14 @@ class RoundLoop:
         (``melissa_amd.env.stream.TestEpisodeStream``; such an env gets a host-drawn table otherwise).
         ``eps_schedule`` (:class:`EpsSchedule`): every round starts with one small launch that computes eps from the envs'
         decision counters and the selection reads that device value instead of ``eps`` - eager rounds and replayed graphs
-        alike, nothing is recaptured when eps changes."""
+        alike, nothing is recaptured when eps changes.
+        ``train_log`` (:class:`melissa_amd.train_log.TrainLog`, built on ``venv`` BEFORE this loop): every round, eager or
+        captured, and every round of a group graph is followed by ``mel_train_log_round``, which folds the episodes the round
+        ended into the log's open record.  None (the default): no such launch."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
+        if train_log is not None and train_log.venv is not venv:
+            raise ValueError("RoundLoop: train_log was built on another env batch")
+        self.train_log = train_log
         self.use_graph, self.graph = use_graph, None
         # run(): whole groups of `graph_rounds` rounds are replayed from ONE HIP graph - a graph launch costs the device ~8 us
         # of idle time between the last kernel of one replay and the first of the next (rocprofv3 kernel trace of the
@@ -232,6 +239,7 @@ class RoundLoop:
             self._bind_plan()
             self.venv.round_device(self.pool, self.act, None, self.live, self.table, round_counter=self.rounds,
                                    replay=self.replay)
+            self._launch_train_log()
             return
         # forward + fused argmax / eps-greedy (the dueling tail writes the action next to the logits)
         # (integer_features: the obs rows are the env kernel's own -> encoder / conv1 projections per feature tuple)
@@ -241,6 +249,12 @@ class RoundLoop:
         self._bind_plan()
         self.venv.round_device(self.pool, self.act, self.offsets, self.live, self.table, round_counter=self.rounds,
                                replay=self.replay)
+        self._launch_train_log()
+
+    def _launch_train_log(self):
+        """The episodes the round just ended, into the training log (with the eps the round was played at)."""
+        if self.train_log is not None:
+            self.train_log.launch_round(self._eps_dev if self.eps_schedule is not None else None)
 
     def _launch_schedule(self):
         """eps of the round about to be played, from the decisions collected before it (read by the selection through

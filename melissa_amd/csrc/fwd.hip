@@ -875,6 +875,7 @@ size_t mel_abi_sizeof(int32_t which) {
         case 11: return sizeof(mel_replay_batch);
         case 12: return sizeof(mel_adam_tensors);
         case 13: return sizeof(mel_replay_priority);
+        case 14: return sizeof(mel_train_log);
         default: return 0;
     }
 }

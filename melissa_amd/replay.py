@@ -345,8 +345,11 @@ class DQNLearner:
     on device tensors, eagerly and inside a captured update; off by default, so every existing caller keeps its launches."""
 
     def __init__(self, policy, replay: RoundReplay, batch_size: int = 32, n_step: int = 4, gamma: float = 0.99,
-                 grad_hook=None, seed: int = 0, fused_td: bool = False):
+                 grad_hook=None, seed: int = 0, fused_td: bool = False, train_log=None):
         self.policy, self.replay, self.fused_td = policy, replay, bool(fused_td)
+        # optional melissa_amd.train_log.TrainLog: every update, eager or captured, launches mel_train_log_update directly in
+        # front of the Adam step (behind the gradient hook: it sees the gradient Adam applies)
+        self.train_log = train_log
         self.batch_size, self.n_step, self.gamma, self.grad_hook = batch_size, n_step, gamma, grad_hook
         self.gen = torch.Generator(device=replay.obs.device)
         self.gen.manual_seed(seed)
@@ -398,6 +401,10 @@ class DQNLearner:
         """``policy.learn`` on a copy of ``batch`` with the priority write-back ahead of the gradient hook; the TD error ends up in
         ``last_batch["td_error"]``."""
         work = dict(batch)
+        if self.train_log is not None:
+            out = self._learn_logged(work)
+            self.last_batch["td_error"] = work["td_error"]
+            return out
 
         def hook(model):
             self.write_back(work)
@@ -408,6 +415,20 @@ class DQNLearner:
         if "td_error" in work:
             self.last_batch["td_error"] = work["td_error"]
         return out
+
+    def _learn_logged(self, work: dict) -> dict:
+        """``policy.learn`` spelled out, with the training log's launch between the gradient hook and the optimizer step."""
+        policy = self.policy
+        if policy._target and policy._iter % policy._freq == 0:
+            policy.sync_weight()
+        loss = policy.loss_backward(work, **self._policy_kwargs())
+        self.write_back(work)
+        if self.grad_hook is not None:
+            self.grad_hook(policy.model)
+        self.train_log.launch_update(loss, work["td_error"], policy.optim)
+        adam_step(policy.optim)
+        policy._iter += 1
+        return {"loss": float(loss)}
 
     def step(self) -> dict:
         if self.captured is not None:
@@ -464,10 +485,11 @@ class CapturedUpdate:
             for _ in range(warmup):
                 self._sync_target()
                 batch = L.sample_batch()
-                policy.loss_backward(batch, **L._policy_kwargs())
+                warm_loss = policy.loss_backward(batch, **L._policy_kwargs())
                 L.write_back(batch)
                 if self.collective:
                     hook.pack(), hook.reduce(), hook.unpack()
+                self._log_update(warm_loss, batch)
                 adam_step(opt)
                 policy._iter += 1
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -481,14 +503,20 @@ class CapturedUpdate:
             if self.collective:
                 hook.pack()
             else:
+                self._log_update(self.loss, self.batch)
                 adam_step(opt)
         self.graph_b = None
         if self.collective:
             self.graph_b = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool()):
                 hook.unpack()
+                self._log_update(self.loss, self.batch)     # (behind unpack: the averaged gradient Adam applies)
                 adam_step(opt)
         L.last_batch = self.batch
+
+    def _log_update(self, loss, batch):
+        if self.learner.train_log is not None:
+            self.learner.train_log.launch_update(loss, batch["td_error"], self.learner.policy.optim)
 
     def _sync_target(self):
         policy = self.learner.policy

@@ -131,7 +131,8 @@ def _evaluate(policy, n_nodes, test_num, eps_test, seed, device, heuristic, scri
     finally:
         policy.model.train(was_training)
     # (the last chunk of rounds may finish an episode more than asked for: the first test_num count)
-    out = dict(rew=float(np.mean(res.returns[:test_num])), len=float(np.mean(res.lens[:test_num])), episodes=int(test_num))
+    out = dict(rew=float(np.mean(res.returns[:test_num])), len=float(np.mean(res.lens[:test_num])), episodes=int(test_num),
+               rew_std=float(np.std(res.returns[:test_num])))
     out.update({k: float(np.mean(res.episode_info[k][:test_num])) for k in _lib.LOGGER_KEYS})
     return out
 
@@ -156,7 +157,8 @@ def _evaluate_spread(policy, n_nodes, test_num, test_envs, eps_test, seed, devic
         res, _positions = evaluate_spread(policy, venv, test_num, eps=eps_test, seed=seed)
     finally:
         policy.model.train(was_training)
-    out = dict(rew=float(np.mean(res.returns)), len=float(np.mean(res.lens)), episodes=int(test_num))
+    out = dict(rew=float(np.mean(res.returns)), len=float(np.mean(res.lens)), episodes=int(test_num),
+               rew_std=float(np.std(res.returns)))
     out.update({k: float(np.mean(res.episode_info[k])) for k in _lib.LOGGER_KEYS})
     return out
 
@@ -234,7 +236,7 @@ def replay_rounds_for(buffer_size: int, envs: int, n_nodes: int) -> int:
 
 
 def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, step_per_epoch, rank, world, device, best_path,
-                last_path, pace=None, pooled=None, state_io=None):
+                last_path, pace=None, pooled=None, state_io=None, train_log=None, log_file=None):
     """The reference's training structure ([3P] tianshou ``OffpolicyTrainer`` as l_dgn.py:246-261 configures it): evaluate, then
     ``epoch`` times [update iterations until ``step_per_epoch`` more env steps are collected; evaluate; keep the best policy], then
     save the last one.  env steps = decisions x ``world``, the decisions being this rank's - with several ranks the smallest
@@ -257,9 +259,27 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     this function's own numbers and records after every epoch's evaluation - after ``before_first_epoch()`` for epoch 0, so
     that every state holds a captured update's two warm-up updates; ``restore()`` replaces the first evaluation: the update is
     captured where a fresh run captures it, then ``restore()`` overwrites everything and hands back the numbers a ``write`` was
-    given, and the loop goes on with the epoch after ``state_epoch``; ``stop_after``: the last epoch this process runs."""
+    given, and the loop goes on with the epoch after ``state_epoch``; ``stop_after``: the last epoch this process runs.
+    ``train_log`` (:class:`melissa_amd.train_log.TrainLog`) / ``log_file``: the log is armed with ``base`` after the first
+    evaluation and the update's capture (warm-up updates are not logged), drained after every epoch's evaluation and before
+    ``write`` - the last epoch of the run with its open interval -, and rank 0 appends the drained rows and one ``test/*`` row
+    per epoch to ``log_file``; the result then carries ``log_file`` and ``log_rows``."""
     import torch
     from . import parallel
+    from .train_log import append_rows
+    log_rows, test_std = 0, [None]
+
+    def log_epoch(index, final=False):
+        """Drain (every rank: the ring must not fill) and, on rank 0, append the rows and the epoch's evaluation."""
+        nonlocal log_rows
+        if train_log is None:
+            return
+        rows = [dict(r, ranks_pooled=1) for r in train_log.drain(final=final)]
+        if rank == 0:
+            rec = epochs[-1]
+            rows.append({"env_step": rec["env_step"], "epoch": index, "test/reward": rec.get("test_rew"),
+                         "test/reward_std": test_std[0], "test/length": rec.get("test_len")})
+            log_rows += append_rows(log_file, rows)
     write, restore, stop_after = state_io if state_io is not None else (None, None, None)
     if rank == 0:
         os.makedirs(os.path.dirname(best_path), exist_ok=True)
@@ -282,7 +302,9 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
                 best = (index, stats["rew"])
                 torch.save(policy.state_dict(), best_path)     # save_best_fn, l_dgn.py:215-222
             rec.update(test_rew=stats["rew"], test_len=stats["len"], best=is_best)
-            rec.update({k: v for k, v in stats.items() if k not in ("rew", "len")})
+            # (rew_std goes to the training log's test row only: the epoch records keep the keys they have always had)
+            test_std[0] = stats.get("rew_std")
+            rec.update({k: v for k, v in stats.items() if k not in ("rew", "len", "rew_std")})
         epochs.append(rec)
         parallel.barrier()
 
@@ -292,6 +314,9 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
         env_step = base = _agreed_decisions(loop, world, device) * world
         test(0, env_step, overshoot=0, updates=0, seconds=0.0, **({} if pace is None else {"update_debt": 0}))
         before_first_epoch()
+        if train_log is not None:
+            train_log.arm(base)
+            log_epoch(0)
         if write is not None:
             write(numbers(0))
     else:
@@ -340,6 +365,7 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
         dt = time.perf_counter() - t0
         updates, seconds = updates + n, seconds + dt
         test(e, env_step, overshoot=env_step - target, updates=n, seconds=dt, **more)
+        log_epoch(e, final=e == epoch)
         if write is not None:
             write(numbers(e))
         if stop_after is not None and e >= stop_after:
@@ -351,6 +377,8 @@ def _run_epochs(loop, policy, iteration, evaluate, before_first_epoch, epoch, st
     result = dict(epochs=epochs, best_epoch=best[0], best_rew=best[1], best_path=best_path, last_path=last_path)
     if pace is not None:
         result["env_steps_per_iteration"] = (env_step - base) / max(1, iterations)
+    if train_log is not None:
+        result.update(log_file=log_file, log_rows=log_rows)
     return [first, last], seconds, updates, result
 
 
@@ -361,7 +389,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
           exploration_fraction=0.6, eps_test=0.001, test_num=100, logdir="log", model_name=None, resume_path=None,
           update_per_step=None, step_per_collect=10, buffer_size=None, test_envs=1, collect_stats="episodes", graph_pool=None,
           hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
-          aggregator_function="max", save_state=False, stop_after_epoch=None, resume_state=None):
+          aggregator_function="max", save_state=False, stop_after_epoch=None, resume_state=None, log_interval=None,
+          log_file=None):
     """``probe(update_index, net, learner, phase)`` (optional) is called with phase "before" / "after" around every
     update - tests use it to re-derive an update's loss from the sampled batch with the oracle.
     ``graphs``: size of the synthetic training-graph dataset (the reference trains on 50 000 graphs per size, README.md:92-93;
@@ -410,9 +439,17 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
     ``state_path``); ``stop_after_epoch=K`` ends the process after epoch K of the ``epoch`` the run has in all (``epoch`` stays
     the total: the eps horizon depends on it); ``resume_state=FILE`` continues the run that wrote FILE from the epoch after
     the one it holds, bit for bit what the uninterrupted run computes.  The file's header must be this call's: a ValueError
-    names the first argument that differs, before anything is built."""
+    names the first argument that differs, before anything is built.
+    ``log_interval`` / ``log_file`` (epoch mode, else ValueError; :mod:`melissa_amd.train_log`, NOTES.md "Training curves"): sum
+    the training curve on the device per ``log_interval`` env steps (the reference's loggers use 1000) - episodes, returns,
+    lengths, eps, loss, TD error, gradient norm - and append it after every epoch, with the epoch's evaluation, to ``log_file``
+    (default ``<logdir>/<model>/<model_name>_progress.jsonl``), one JSON object per line; a resumed run appends to the file.  Each
+    rank sums its own envs, rank 0 writes its rows (``"ranks_pooled": 1``).  The result gains ``log_file`` and ``log_rows``.
+    Without ``log_interval`` no launch is added and no buffer allocated."""
     from . import train_state
+    from .train_log import check_log_args
     train_state.check_resume_args(epoch, save_state, stop_after_epoch, resume_state, resume_path)
+    check_log_args(epoch, log_interval, log_file)
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function)
     if collect_stats not in ("episodes", "steps"):
         raise ValueError(f"collect_stats={collect_stats!r}: 'episodes' or 'steps'")
@@ -463,7 +500,8 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
             eps_train=eps_train, eps_train_final=eps_train_final, exploration_fraction=exploration_fraction,
             update_per_step=None if update_per_step is None else float(update_per_step), step_per_collect=int(step_per_collect),
             replay_rounds=int(replay_rounds), rounds_per_update=int(rounds_per_update), ring=int(ring), seed=int(seed),
-            captured=captured, collect_stats=collect_stats, mel_version=_lib.load().mel_version().decode())
+            captured=captured, collect_stats=collect_stats, mel_version=_lib.load().mel_version().decode(),
+            **({} if log_interval is None else {"log_interval": int(log_interval)}))
     if resume_state is not None:
         # the header is compared before the network, the envs or a graph exist (the file is memory-mapped: reading the header
         # reads no tensor); the training pool's identity follows as soon as there is a pool
@@ -506,6 +544,14 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
         def pooled():
             count, stats = venv.read_step_stats(reset=True)
             return dict(train_info_rows=count, **{f"train_{k}": v.mean for k, v in stats.items()})
+    train_log = None
+    if log_interval is not None:
+        # before the loop is built: every captured round holds the episode log's pointers.  The ring holds an epoch's intervals
+        # and what the loop may run past its target (the end of an epoch is noticed an iteration late: two iterations' decisions)
+        from .train_log import TrainLog, ring_capacity
+        overshoot = 2 * max(1, rounds_per_update) * envs * n_nodes * world
+        train_log = TrainLog(venv, int(log_interval), ring_capacity(step_per_epoch, log_interval, overshoot), scale=world,
+                             device=device)
     if prio_buffer:
         replay = PrioritizedRoundReplay(envs, n_nodes, replay_rounds, device, neighbours=neighbours, alpha=alpha, beta=beta)
     else:
@@ -519,9 +565,10 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                                epoch=int(epoch), step_per_epoch=int(step_per_epoch), scale=world)
     loop = RoundLoop(venv, policy, seed=1000 + rank * envs, eps=eps, replay=replay, ring=ring,
                      use_graph=device.type == "cuda" and probe is None, graph_rounds=max(1, rounds_per_update),
-                     eps_schedule=schedule)
+                     eps_schedule=schedule, **({} if train_log is None else {"train_log": train_log}))
     learner = learner_cls(policy, replay, batch_size=batch_size, n_step=n_step, gamma=gamma,
-                         grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank, **({"fused_td": True} if paced else {}))
+                         grad_hook=parallel.FlatGradAllReducer(net), seed=seed + rank, **({"fused_td": True} if paced else {}),
+                         **({} if train_log is None else {"train_log": train_log}))
     with torch.no_grad():
         loop.run(max(n_step + 1, 8))                           # pre-fill (l_dgn.py:201)
     warmup_updates = 2 if captured else 0
@@ -571,6 +618,9 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
             return stats
         weights_dir = os.path.join(logdir, model, "weights")
         name = model_name if model_name is not None else default_model_name()
+        if train_log is not None and log_file is None:
+            from .train_log import default_log_file
+            log_file = default_log_file(logdir, model, name)
         # (epoch mode captures the update AFTER the first evaluation: `param_checksum_start`, that evaluation and the first
         # _best.pth are all of the policy no update has touched)
         state_path = train_state.rank_state_path(os.path.join(weights_dir, f"{name}_state.pth"), rank, world)
@@ -579,12 +629,12 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
             os.makedirs(weights_dir, exist_ok=True)
             config = dict(header, state_epoch=numbers["state_epoch"])
             numbers = dict(numbers, param_checksum_start=checksum_start)
-            train_state.write_state_file(train_state.gather_state(config, numbers, policy, learner, replay, loop, venv, device),
-                                         state_path)
+            train_state.write_state_file(train_state.gather_state(config, numbers, policy, learner, replay, loop, venv, device,
+                                                                  train_log=train_log), state_path)
 
         def restore_state():
             nonlocal checksum_start
-            numbers = train_state.restore_state(saved, policy, learner, replay, loop, venv, device)
+            numbers = train_state.restore_state(saved, policy, learner, replay, loop, venv, device, train_log=train_log)
             checksum_start = numbers["param_checksum_start"]
             return numbers
 
@@ -594,7 +644,7 @@ def train(model="hl_dgn", n_nodes=20, envs=256, updates=20, rounds_per_update=4,
                                                  world, device, os.path.join(weights_dir, f"{name}_best.pth"),
                                                  os.path.join(weights_dir, f"{name}_last.pth"),
                                                  pace=(collect, update, float(update_per_step)) if paced else None,
-                                                 pooled=pooled, state_io=state_io)
+                                                 pooled=pooled, state_io=state_io, train_log=train_log, log_file=log_file)
         extra["param_checksum_start"] = checksum_start
         if save_state:
             extra["state_path"] = state_path
@@ -689,6 +739,12 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--resume-state", type=str, default=None, metavar="FILE",
                     help="continue the run that wrote FILE (--save-state) from the epoch after the one it holds; every other "
                          "argument must be that run's")
+    # the training curve (the reference's loggers write about every 1000 env steps, l_dgn.py:203-213)
+    ap.add_argument("--log-interval", type=int, default=None, metavar="N",
+                    help="sum the training curve on the device per N env steps (the reference: 1000) and append it, with every "
+                         "epoch's evaluation, to --log-file as JSON lines; needs --epoch")
+    ap.add_argument("--log-file", type=str, default=None, metavar="FILE",
+                    help="default <logdir>/<model>/<model-name>_progress.jsonl; a resumed run appends")
     # the reference's network flags, names and defaults (common.py:29-30,41-43)
     ap.add_argument("--hidden-emb", type=int, default=128, help="encoder width and channels per attention head")
     ap.add_argument("--num-heads", type=int, default=4, help="attention heads (a power of two, or 6)")
@@ -718,7 +774,8 @@ def train_kwargs(a: argparse.Namespace) -> dict:
                 test_envs=a.test_envs, collect_stats=a.collect_stats, graph_pool=a.graph_pool,
                 hidden_emb=a.hidden_emb, num_heads=a.num_heads, dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
                 dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
-                save_state=a.save_state, stop_after_epoch=a.stop_after_epoch, resume_state=a.resume_state)
+                save_state=a.save_state, stop_after_epoch=a.stop_after_epoch, resume_state=a.resume_state,
+                log_interval=a.log_interval, log_file=a.log_file)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -736,6 +793,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     from . import train_state
     try:
         train_state.check_resume_args(a.epoch, a.save_state, a.stop_after_epoch, a.resume_state, a.resume_path)
+    except ValueError as e:
+        ap.error(str(e))
+    from .train_log import check_log_args
+    try:
+        check_log_args(a.epoch, a.log_interval, a.log_file)
     except ValueError as e:
         ap.error(str(e))
     import sys

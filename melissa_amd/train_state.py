@@ -26,6 +26,8 @@ HEADER_KEYS = ("model", "n_nodes", "envs", "world", "rank", "hidden_emb", "num_h
                "prio_buffer", "alpha", "beta", "heuristic", "scripted_agents_ratio", "epoch", "step_per_epoch", "eps_train",
                "eps_train_final", "exploration_fraction", "update_per_step", "step_per_collect", "replay_rounds",
                "rounds_per_update", "ring", "seed", "captured", "collect_stats", "pool_graphs", "pool_checksum", "mel_version")
+# header keys only a run with the feature on carries (a file without the feature has exactly HEADER_KEYS): compared both ways
+OPTIONAL_HEADER_KEYS = ("log_interval",)
 
 
 class StateMismatch(ValueError):
@@ -50,11 +52,11 @@ def check_resume_args(epoch=None, save_state=False, stop_after_epoch=None, resum
 def state_header(**values) -> dict:
     """The header of a run: exactly :data:`HEADER_KEYS`, as plain numbers / strings / lists (``pool_graphs`` and
     ``pool_checksum`` may be left out until the training pool exists: :func:`pool_identity`)."""
-    unknown = set(values) - set(HEADER_KEYS)
+    unknown = set(values) - set(HEADER_KEYS) - set(OPTIONAL_HEADER_KEYS)
     if unknown:
         raise KeyError(f"not header keys: {sorted(unknown)}")
     out = {}
-    for key in HEADER_KEYS:
+    for key in HEADER_KEYS + OPTIONAL_HEADER_KEYS:
         if key not in values:
             continue
         v = values[key]
@@ -89,6 +91,9 @@ def check_state_header(saved: dict, wanted: dict, path: str = "the state file") 
             raise StateMismatch(f"{path} has no {key} in its header (this call: {key}={wanted[key]!r})")
         if saved[key] != wanted[key]:
             raise StateMismatch(f"{path} was written by a run with {key}={saved[key]!r}; this call has {key}={wanted[key]!r}")
+    for key in OPTIONAL_HEADER_KEYS:
+        if "epoch" in wanted and saved.get(key) != wanted.get(key):
+            raise StateMismatch(f"{path} was written by a run with {key}={saved.get(key)!r}; this call has {key}={wanted.get(key)!r}")
     if "epoch" in wanted and int(saved.get("state_epoch", -1)) >= int(wanted["epoch"]):
         raise StateMismatch(f"{path} holds the state after epoch {saved.get('state_epoch')}: nothing is left of a run of "
                             f"epoch={wanted['epoch']}")
@@ -170,9 +175,10 @@ def quiesce(loop, device) -> None:
     torch.cuda.synchronize(device)
 
 
-def gather_state(config: dict, run: dict, policy, learner, replay, loop, venv, device) -> dict:
+def gather_state(config: dict, run: dict, policy, learner, replay, loop, venv, device, train_log=None) -> dict:
     """Host copy of the whole training state (see the module docstring); ``config``: the header with ``state_epoch``,
-    ``run``: the epoch loop's own numbers and records."""
+    ``run``: the epoch loop's own numbers and records; ``train_log``: the run's training log, whose ring and drain position
+    the state then holds (key ``train_log``; absent without one)."""
     import torch
     quiesce(loop, device)
     replay.sampler_scratch()                                 # (an eager run that has not sampled yet: the draw counter, at 0)
@@ -184,8 +190,9 @@ def gather_state(config: dict, run: dict, policy, learner, replay, loop, venv, d
         stream["pool"] = {k: v.detach().cpu() for k, v in pool.tensors.items()}
         if pool.snapshot_state is not None:
             stream["snapshot_state"] = pool.snapshot_state.cpu()
+    more = {} if train_log is None else {"train_log": train_log.state()}
     return dict(
-        format=FORMAT, config=_plain(dict(config)), run=_plain(dict(run)),
+        **more, format=FORMAT, config=_plain(dict(config)), run=_plain(dict(run)),
         policy=dict(state_dict={k: v.detach().cpu() for k, v in policy.state_dict().items()}, iter=int(policy._iter),
                     optim=_optim_to_host(policy.optim.state_dict())),
         learner=dict(gen=learner.gen.get_state().cpu()),
@@ -233,7 +240,7 @@ def _restore_optim(opt, saved: dict) -> None:
                 own[k] = v
 
 
-def restore_state(state: dict, policy, learner, replay, loop, venv, device) -> dict:
+def restore_state(state: dict, policy, learner, replay, loop, venv, device, train_log=None) -> dict:
     """Overwrite the run built here with ``state`` (a loaded file), in place; -> its ``run`` part.  The caller has built the run
     as a fresh one would be, played the pre-fill rounds and captured the update, so every lazily created tensor and graph
     exists; what those steps did is overwritten."""
@@ -257,6 +264,11 @@ def restore_state(state: dict, policy, learner, replay, loop, venv, device) -> d
         _put_all(loop, _LOOP, state["loop"], "loop")
         loop.iterations, loop._rounds_base = int(state["loop"]["iterations"]), int(state["loop"]["rounds_base"])
         _put_all(venv, _VENV, state["venv"], "venv")
+        if (train_log is None) != ("train_log" not in state):
+            raise ValueError("state file: it " + ("holds" if "train_log" in state else "has no") + " training log, the run built "
+                             "here " + ("has none" if train_log is None else "has one"))
+        if train_log is not None:
+            train_log.load_state(state["train_log"])
         supply, saved = loop.supply, state["stream"]
         _put_all(supply, _STREAM, saved, "stream")
         if hasattr(supply, "refills"):
