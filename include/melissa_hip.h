@@ -136,7 +136,17 @@ typedef struct mel_weights {
  * hidden layers) and the weight matrices of the dense projections are bf16 (the fp32 nn.Parameters are
  * converted into the workspace by every call), contractions run on the bf16 MFMA with fp32 accumulation;
  * attention scores / softmax / aggregation, biases, the encoder's first layer, the last head layer and the
- * logits stay fp32.  Not the reference's arithmetic: expect ~1e-2 absolute on logits (tests state the bound). */
+ * logits stay fp32.  Not the reference's arithmetic: expect ~1e-2 absolute on logits (tests state the bound).
+ * The same holds for HL-DGN (pooled head input in bf16).  Exactly where a value is rounded to bf16 (round to nearest even):
+ *   - the projection weights: encoder layer 1, lin_l / lin_r / lin_v of the convs, every hidden head layer but see below;
+ *   - the first encoder layer's OUTPUT relu(W0 x + b0) (fp32 weights, fp32 fma chain over the features in order), as it
+ *     becomes the bf16 operand of layer 1; then the encoder output, each conv projection (+ bias), relu(conv + bias) of
+ *     conv1 BEFORE the decision-maker mask (x_2) and, separately, that fp32 value times the flag (the conv1 rows conv2
+ *     reads), relu(conv2 + bias) (x_3), HL-DGN's pooled row (the mask and the max / mean / add run in fp32 on unrounded rows);
+ *   - the output of a hidden head layer, EXCEPT the last hidden layer, which is stored fp32 for the fp32 tail.
+ *   The standard heads (two hidden layers of 128 for Q and for V) round less: their first layer's bf16 products are kept in
+ *   fp32, and bias + ReLU, the second hidden layer (on the fp32 parameters) and the tail run in fp32 in one launch.
+ *   A head without a hidden layer (out_linear) is refused: MEL_ERR_UNSUPPORTED. */
 #define MEL_PREC_F32  0
 #define MEL_PREC_BF16 1
 /* MEL_PREC_F32_SPLIT: fp32 features and fp32-accurate results, with the dense projections evaluated on the bf16 matrix
@@ -378,7 +388,40 @@ mel_status mel_hldgn_forward_envs(const mel_weights* w, int32_t aggregator, cons
  *       3 = int32 [1 + bs]: [0] rows of the node-feature table the last forward used (0 = row-list path),
  *           [1 + b] = 1 if env b had a node feature outside the integer ranges of MEL_FWD_INTEGER_FEATURES.
  * rows_cap: 0 for a workspace used by mel_ldgn_forward / mel_hldgn_forward, else the rows_cap given to
- * mel_ldgn_forward_agents.  `out` is a device pointer with room for the requested tensor. */
+ * mel_ldgn_forward_agents.  `out` is a device pointer with room for the requested tensor.
+ *
+ * Kinds MEL_TAP_H0 .. MEL_TAP_ENC0: the feature-row buffers between the stages, each copied WHOLE (the rows the workspace
+ * layout gives it, live or not - rows past the live count hold whatever the workspace held) in the buffer's own element
+ * type E: bf16 when w->precision is MEL_PREC_BF16, else fp32.  Row-major, leading dimension = the row width given below.
+ * Row orders: "U2 rows" / "U1 rows" = the packed row lists of the plan (per env in node-id order, envs in order; live counts
+ * by kind 2), "agent rows" = the logits' row order.  Caps: U2 rows bs * n_nodes; U1 rows bs * min(n_nodes, 34) for
+ * rows_cap = 0, else bs * n_nodes; agent rows bs for rows_cap = 0, else rows_cap.  HL-DGN has no row lists: its rows are
+ * all bs * n_nodes nodes, row b * n_nodes + i.
+ *   MEL_TAP_H0   encoder output                      [U2 rows, hidden] E          (HL-DGN: [bs * n_nodes, hidden])
+ *   MEL_TAP_XL1  conv1 source-side projections       [U2 rows, srcw] E: srcw = heads * C for GATv2 (lin_l), 2 heads * C for
+ *                TransformerConv (key | value) and for HL-DGN (lin_l | lin_r of every node)
+ *   MEL_TAP_XR1  conv1 target-side projection        [U1 rows, heads * C] E       (lin_r / query; not HL-DGN)
+ *   MEL_TAP_H1   conv1 output times the decision-maker flag [U1 rows, heads * C] E (not HL-DGN; fp32 precisions: bf16 planes
+ *                instead of rows where conv2 runs on the planes kernel)
+ *   MEL_TAP_XL2  conv2 source-side projections       [U1 rows, srcw] E            (not HL-DGN)
+ *   MEL_TAP_XR2  conv2 target-side projection        [agent rows, heads * C] E    (not HL-DGN)
+ *   MEL_TAP_HQ0, MEL_TAP_HQ1  the heads' hidden ping-pong buffers, agent rows * hw * 4 BYTES each (hw = widest hidden Q layer
+ *                + widest hidden V layer).  Hidden layer i writes buffer i & 1 from its start as [agent rows, q_i + v_i]
+ *                (Q | V side by side), bf16 on the bf16 path EXCEPT the last hidden layer, which is fp32 (the tail reads
+ *                fp32); fp32 otherwise.  The standard heads (hidden [128, 128] for Q and V) do not use them: see MEL_PREC_BF16.
+ *   MEL_TAP_ENC0 first encoder layer's rows [U2 rows, K0] E, only where the encoder is wider than 256 and they live in a
+ *                buffer of their own; else MEL_ERR_UNSUPPORTED, as is every kind whose buffer the model does not have.
+ * These kinds are defined for the row-list path only: with MEL_FWD_INTEGER_FEATURES in w->flags they return
+ * MEL_ERR_UNSUPPORTED (in table mode the first three buffers hold table rows; tests hold that path to the row lists' bits). */
+#define MEL_TAP_H0   4
+#define MEL_TAP_XL1  5
+#define MEL_TAP_XR1  6
+#define MEL_TAP_H1   7
+#define MEL_TAP_XL2  8
+#define MEL_TAP_XR2  9
+#define MEL_TAP_HQ0  10
+#define MEL_TAP_HQ1  11
+#define MEL_TAP_ENC0 12
 mel_status mel_forward_tap(const mel_weights* w, int32_t kind, int64_t bs, int32_t n_nodes, int64_t rows_cap,
                            const void* workspace, void* out, void* stream);
 

@@ -1199,6 +1199,29 @@ mel_status mel_forward_tap(const mel_weights* w, int32_t kind, int64_t bs, int32
         int32_t* o = static_cast<int32_t*>(out);
         e = hipMemcpyAsync(o, L.plan.fmeta, sizeof(int32_t), hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(o + 1, L.plan.fbad, (size_t)bs * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+    } else if (kind >= MEL_TAP_H0 && kind <= MEL_TAP_ENC0) {
+        // the feature-row buffers of the row-list path, each in its own element type, up to the rows carve() gave it
+        if (w->flags & MEL_FWD_INTEGER_FEATURES)
+            return fail(MEL_ERR_UNSUPPORTED, "tap kind %d is defined for the row-list path only", kind);
+        const NetShape z = shape_of(w);
+        const size_t es = z.bf ? sizeof(uint16_t) : sizeof(float);
+        const size_t M = (size_t)bs * n, R = (size_t)d.rows_cap, U1 = (size_t)d.u1_cap, U2 = z.hl ? M : (size_t)d.u2_cap;
+        const int hw = head_hidden_width(w->q_head) + head_hidden_width(w->v_head);
+        const void* src = nullptr;
+        size_t bytes = 0;
+        switch (kind) {
+            case MEL_TAP_H0: src = L.h0, bytes = U2 * z.hidden * es; break;
+            case MEL_TAP_XL1: src = L.xl1, bytes = U2 * z.srcw * es; break;
+            case MEL_TAP_XR1: src = L.xr1, bytes = U1 * z.hc * es; break;
+            case MEL_TAP_H1: src = L.h1, bytes = U1 * z.hc * es; break;
+            case MEL_TAP_XL2: src = L.xl2, bytes = U1 * z.srcw * es; break;
+            case MEL_TAP_XR2: src = L.xr2, bytes = R * z.hc * es; break;
+            case MEL_TAP_HQ0: src = L.hq[0], bytes = R * (hw > 0 ? hw : 1) * sizeof(float); break;
+            case MEL_TAP_HQ1: src = L.hq[1], bytes = R * (hw > 0 ? hw : 1) * sizeof(float); break;
+            default: src = L.enc0, bytes = U2 * z.K0 * es; break;
+        }
+        if (!src) return fail(MEL_ERR_UNSUPPORTED, "tap kind %d: this model / shape has no such buffer", kind);
+        e = hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s);
     } else
         return fail(MEL_ERR_INVALID_ARG, "unknown tap kind %d", kind);
     if (e != hipSuccess) return fail(MEL_ERR_LAUNCH, "tap copy: %s", hipGetErrorString(e));

@@ -338,6 +338,33 @@ class HipForwardMixin:
                                        _lib.current_stream_ptr(ws.device)), "mel_forward_tap")
         return out
 
+    # mel_forward_tap kinds MEL_TAP_H0 .. MEL_TAP_ENC0 (include/melissa_hip.h): the feature-row buffers between the stages
+    STAGE_TAPS = {"h0": 4, "xl1": 5, "xr1": 6, "h1": 7, "xl2": 8, "xr2": 9, "hq0": 10, "hq1": 11, "enc0": 12}
+
+    def hip_stage_tap(self, name: str, bs: int, rows_cap: int = 0, workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """One of the feature-row buffers of the last row-list forward with this workspace, WHOLE (the rows past the live
+        count included), in its own element type: ``[cap rows, width]`` bf16 on the bf16 feature path, else fp32 - shapes, row
+        orders and caps as documented at MEL_TAP_H0 in the header.  ``hq0`` / ``hq1`` come back as raw bytes ``[agent rows,
+        4 * hw]`` (a layer's element type depends on its place in the head).  Raises where the model has no such buffer."""
+        lib = _lib.load()
+        w = self._weights()
+        ws = workspace if workspace is not None else (self._ws_agents if rows_cap else self._ws)
+        n, hl = self.agents_num, self._MODEL == _lib.MODEL_HLDGN
+        hidden, hc = w.encoder.layer[1].out_dim, w.conv1.heads * w.conv1.channels
+        srcw = 2 * hc if hl or w.conv1.kind == _lib.CONV_TRANSFORMER else hc
+        rows = rows_cap or bs
+        u2 = bs * n
+        u1 = bs * n if rows_cap else bs * min(n, 34)
+        hidden_width = lambda m: max([m.layer[i].out_dim for i in range(m.n_layers - 1)], default=0)
+        hw = max(hidden_width(w.q_head) + hidden_width(w.v_head), 1)
+        shape = {"h0": (u2, hidden), "xl1": (u2, srcw), "xr1": (u1, hc), "h1": (u1, hc), "xl2": (u1, srcw), "xr2": (rows, hc),
+                 "hq0": (rows, 4 * hw), "hq1": (rows, 4 * hw), "enc0": (u2, w.encoder.layer[0].out_dim)}[name]
+        dtype = torch.uint8 if name in ("hq0", "hq1") else torch.bfloat16 if self.feature_dtype == "bf16" else torch.float32
+        out = torch.empty(shape, dtype=dtype, device=ws.device)
+        _lib.check(lib.mel_forward_tap(C.byref(w), self.STAGE_TAPS[name], bs, n, rows_cap, ws.data_ptr(), out.data_ptr(),
+                                       _lib.current_stream_ptr(ws.device)), "mel_forward_tap")
+        return out
+
     def plan_pointers(self, bs: int, rows_cap: int, workspace: torch.Tensor):
         """Device addresses (adj, live, u1, u2, cnt) of the plan masks inside ``workspace`` for a forward of these dimensions
         (``rows_cap`` = 0: the hip_forward / hip_forward_envs layout) - the values of mel_env_batch.plan_*."""
