@@ -1031,6 +1031,101 @@ mel_status mel_train_log_round(const mel_train_log* log, const mel_env_batch* en
 mel_status mel_train_log_update(const mel_train_log* log, const float* loss, const float* td, int64_t batch,
                                 const mel_adam_tensors* grads, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-round dissemination curves and node traces of an evaluation, recorded ON THE DEVICE: what the reference shows by drawing
+ * the graph after every world step (graph.py:350-356, draw_graph :466-484).  The rounds replay from HIP graphs and nothing reads
+ * the device between them, so one capturable launch behind every mel_env_round samples the state the round left.  An env's loop
+ * inside mel_env_round ends at a world step or at an episode end with reset: the state a launch sees is either "after world
+ * step num_moves of the current episode" or "the new episode's reset state, num_moves == 0".  When the observation right after
+ * a world step raises explicit_reset (graph.py:205-211) the episode ends in the launch of its last world step and that state
+ * is gone; its figures are in the env batch's episode log (mel_env_batch.log_*: final logger_stats and num_moves), which the
+ * recorder therefore NEEDS: the log must be on, large enough not to drop rows (rows are only looked up, never consumed), and
+ * not emptied by another launch between a round and the recorder's launch (mel_train_log_round does that: not both).
+ * All pointers of mel_round_record are caller-owned DEVICE memory (B = n_envs, R = max_rounds, N = n_nodes, W = MEL_SET_WORDS(N)):
+ *   running   double [B][R][MEL_RR_FIELDS]  sum of the samples env b took at round index r                       (start: 0)
+ *   ended     double [B][R][MEL_RR_FIELDS]  sum of the FINAL rows of env b's ended episodes, at their last round index (start: 0)
+ *   seen      int32  [B][MEL_RR_CARRY]      the env's carry: MEL_S_EPISODES_DONE and MEL_S_NUM_MOVES of the state sampled last,
+ *                                           the round index of the running episode's last sample (-1: none), whether every
+ *                                           interested node held the message at it, the episode-log rows looked at so far,
+ *                                           one reserved                                                         (start: all -1)
+ *   last      double [B][MEL_RR_FIELDS]     the running episode's last sample
+ *   overflow  int64  [B]   rows not stored because their round index was >= R (a sample, or an episode's final row)  (start: 0)
+ *   skipped   int64  [B]   launches that found the env with MEL_S_ERROR != 0                                     (start: 0)
+ *   unlogged  int64  [B]   ended episodes whose row was not in the episode log (it was full)                     (start: 0)
+ *   quota     int32  [B]   optional (NULL: no limit): episodes of env b that count
+ * mel_round_record_round, per env (one wavefront, 4 envs per 256-lane workgroup, no atomics - an env owns its rows):
+ *   - (episodes_done, num_moves) equal to the carry: nothing (a second launch on the same state is idempotent);
+ *   - else MEL_S_ERROR != 0: skipped[b] += 1, nothing else;
+ *   - else, episodes_done differs from the carry's: the previous episode has ended.  If it has a last sample, the env's newest
+ *     row among the episode-log rows it has not looked at yet gives the episode's final num_moves and the logger_stats of its
+ *     final observation (the selected agent's slot as stored: what an evaluation reports for the episode), as a row of fields
+ *     0 .. 7 = 1, round(coverage * N), coverage_interested_count, interested_agents, total_messages_transmitted, 0 (nobody
+ *     acts any more), coverage_interested_fraction, newly covered by the rule below.  Where the final num_moves is not the last
+ *     sample's round, that row is the episode's final sample: added to running[b][num_moves] (it has no trace record: the node
+ *     state is gone) and to ended[b][num_moves].  Otherwise ended[b][last round] takes `last` with fields 1 - 4 and 6 from the
+ *     row.  So per env the ended sums of fields 4 and 6 ARE the sums of its episode-log rows, added in play order.  The episode
+ *     carry is cleared.  No row (a full log): unlogged[b] += 1 and `last` is booked as it stands;
+ *   - then, unless quota && episodes_done >= quota[b], ONE sample at round index r = num_moves, MEL_RR_FIELDS doubles:
+ *       0 count 1;  1 |has_message|;  2 |has_message & interested|;  3 |interested|;  4 MEL_S_WORLD_MSGS;  5 |MEL_SEL_ACTIVE|;
+ *       6 coverage_interested_fraction as get_info computes it (graph.py:158-162): field 2 / field 3 in one double division, 0
+ *         when no node is interested;
+ *       7 newly covered: 1 when every interested node (at least one) holds the message and that was not so at the episode's
+ *         previous sample, else 0
+ *     added to running[b][r], kept as `last`; the carry takes the state.  All fields but 6 are integers: their sums are exact in
+ *     any order; field 6 is summed per env in play order.  An env past its quota still books the end of its last counted episode.
+ *   - trace sink (n_trace > 0): trace_env[t] lists up to MEL_RR_MAX_TRACE distinct envs (VALUES inside the struct, checked on the
+ *     host), each with a ring of trace_capacity records.  Every sample a listed env takes (stored or overflowed) also writes
+ *     record trace_cursor[t] % trace_capacity and advances trace_cursor[t] (int64, start: 0).  Struct-of-arrays, record rec =
+ *     t * trace_capacity + slot:
+ *       trace_meta       int32  [T][cap][8]     env, episode ordinal (episodes_done), MEL_S_EPISODE, num_moves, MEL_S_ORIGIN,
+ *                                               MEL_S_WORLD_MSGS, 0, 0
+ *       trace_pos        double [T][cap][N][2]
+ *       trace_one_hop    uint64 [T][cap][N][W]
+ *       trace_sets       uint64 [T][cap][6][W]  has_message, origin, interested, scripted, MEL_SEL_ACTIVE, MEL_SEL_TAKEN_ACTION
+ *       trace_agent_msgs int32  [T][cap][N]
+ *       trace_received   int32  [T][cap][N]
+ * mel_round_record_read: running_out / ended_out device double [R][MEL_RR_FIELDS] = the envs' rows added in ascending env order
+ *   (a thread per (round, field): equal inputs give equal bits), counters_out device int64 [4] = MEL_RRC_*: the sums of overflow,
+ *   skipped and unlogged, one reserved.
+ * Neither reads on the host nor allocates: both replay from a HIP graph.  MEL_ERR_INVALID_ARG: a null record / buffer / env /
+ * output, an env batch without an episode log, max_rounds outside [1, MEL_RR_MAX_ROUNDS], n_envs or n_nodes other than the env batch's, n_trace outside
+ * [0, MEL_RR_MAX_TRACE], a traced env outside [0, n_envs) or listed twice, trace_capacity < 1 or a null trace buffer with
+ * n_trace > 0. */
+#define MEL_RR_FIELDS      8
+#define MEL_RR_CARRY       6
+#define MEL_RR_MAX_TRACE  16
+#define MEL_RR_MAX_ROUNDS (1 << 20)
+#define MEL_RRC_OVERFLOW   0
+#define MEL_RRC_SKIPPED    1
+#define MEL_RRC_UNLOGGED   2
+typedef struct mel_round_record {
+    double*        running;
+    double*        ended;
+    int32_t*       seen;
+    double*        last;
+    int64_t*       overflow;
+    int64_t*       skipped;
+    int64_t*       unlogged;
+    const int32_t* quota;
+    int64_t*       trace_cursor;
+    int32_t*       trace_meta;
+    double*        trace_pos;
+    uint64_t*      trace_one_hop;
+    uint64_t*      trace_sets;
+    int32_t*       trace_agent_msgs;
+    int32_t*       trace_received;
+    int32_t        n_envs;
+    int32_t        n_nodes;
+    int32_t        max_rounds;
+    int32_t        n_trace;
+    int32_t        trace_capacity;
+    int32_t        reserved;
+    int32_t        trace_env[MEL_RR_MAX_TRACE];
+} mel_round_record;
+mel_status mel_round_record_round(const mel_round_record* rec, const mel_env_batch* env, void* stream);
+mel_status mel_round_record_read(const mel_round_record* rec, double* running_out, double* ended_out, int64_t* counters_out,
+                                 void* stream);
+
 /* last() only (mutates is_new_round exactly like GraphEnv.observe, graph.py:205-211). */
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n,
                            const mel_env_obs* out, void* stream);
@@ -1068,7 +1163,7 @@ const char* mel_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, for binding authors to check their mirrors
  * against: which = 0 mel_linear, 1 mel_gatv2, 2 mel_mlp, 3 mel_weights, 4 mel_select, 5 mel_env_batch,
  * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors,
- * 13 mel_replay_priority, 14 mel_train_log;
+ * 13 mel_replay_priority, 14 mel_train_log, 15 mel_round_record;
  * 0 for anything else. */
 size_t mel_abi_sizeof(int32_t which);
 const char* mel_version(void);

@@ -44,7 +44,7 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
            "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
            "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate", "mel_train_log_scratch_bytes",
-           "mel_train_log_round", "mel_train_log_update")
+           "mel_train_log_round", "mel_train_log_update", "mel_round_record_round", "mel_round_record_read")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -123,6 +123,23 @@ class MelTrainLog(C.Structure):
     _fields_ = [("records", C.c_void_p), ("interval_id", C.c_void_p), ("counters", C.c_void_p), ("base", C.c_void_p),
                 ("drained_upto", C.c_void_p), ("decisions", C.c_void_p), ("interval", C.c_int64), ("capacity", C.c_int32),
                 ("stride", C.c_int32), ("n_envs", C.c_int32), ("scale", C.c_uint32)]
+
+
+# mel_round_record: the sample layout (MEL_RR_*), the read counters (MEL_RRC_*) and the struct
+RR_FIELDS, RR_CARRY, RR_MAX_TRACE, RR_MAX_ROUNDS = 8, 6, 16, 1 << 20
+(RR_COUNT, RR_HAS_MESSAGE, RR_INTERESTED_WITH_MESSAGE, RR_INTERESTED, RR_MESSAGES, RR_ACTIVE, RR_COVERAGE_FRACTION,
+ RR_NEWLY_COVERED) = range(8)
+RRC_OVERFLOW, RRC_SKIPPED, RRC_UNLOGGED = 0, 1, 2
+RR_TRACE_SETS = ("has_message", "origin", "interested", "scripted", "active", "taken_action")
+
+
+class MelRoundRecord(C.Structure):
+    _fields_ = [("running", C.c_void_p), ("ended", C.c_void_p), ("seen", C.c_void_p), ("last", C.c_void_p),
+                ("overflow", C.c_void_p), ("skipped", C.c_void_p), ("unlogged", C.c_void_p), ("quota", C.c_void_p), ("trace_cursor", C.c_void_p),
+                ("trace_meta", C.c_void_p), ("trace_pos", C.c_void_p), ("trace_one_hop", C.c_void_p), ("trace_sets", C.c_void_p),
+                ("trace_agent_msgs", C.c_void_p), ("trace_received", C.c_void_p), ("n_envs", C.c_int32), ("n_nodes", C.c_int32),
+                ("max_rounds", C.c_int32), ("n_trace", C.c_int32), ("trace_capacity", C.c_int32), ("reserved", C.c_int32),
+                ("trace_env", C.c_int32 * RR_MAX_TRACE)]
 
 
 class MelEnvBatch(C.Structure):
@@ -296,6 +313,10 @@ def load(build_if_missing: bool = True):
     lib.mel_train_log_round.argtypes = [C.POINTER(MelTrainLog), E, vp, vp]
     lib.mel_train_log_update.restype = i32
     lib.mel_train_log_update.argtypes = [C.POINTER(MelTrainLog), vp, vp, i64, C.POINTER(MelAdamTensors), vp, sz, vp]
+    lib.mel_round_record_round.restype = i32
+    lib.mel_round_record_round.argtypes = [C.POINTER(MelRoundRecord), E, vp]
+    lib.mel_round_record_read.restype = i32
+    lib.mel_round_record_read.argtypes = [C.POINTER(MelRoundRecord), vp, vp, vp, vp]
     lib.mel_mpr_sets.restype = i32
     lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz

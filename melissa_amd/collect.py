@@ -146,7 +146,7 @@ class RoundLoop:
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
                  stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: "bool | str | None" = None,
                  ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None,
-                 train_log=None):
+                 train_log=None, recorder=None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
         ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes;
@@ -157,8 +157,18 @@ class RoundLoop:
         alike, nothing is recaptured when eps changes.
         ``train_log`` (:class:`melissa_amd.train_log.TrainLog`, built on ``venv`` BEFORE this loop): every round, eager or
         captured, and every round of a group graph is followed by ``mel_train_log_round``, which folds the episodes the round
-        ended into the log's open record.  None (the default): no such launch."""
+        ended into the log's open record.  None (the default): no such launch.
+        ``recorder`` (:class:`melissa_amd.round_record.RoundRecorder` on ``venv``): every round, eager or captured, is followed
+        by ``mel_round_record_round``, which samples the state the round left into the recorder's per-round curves and traces;
+        one more launch behind the constructor's ``first`` launch records the first episodes' round 0.  None (the default): no
+        such launch, the sequence is the one without the recorder."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
+        if recorder is not None and recorder.venv is not venv:
+            raise ValueError("RoundLoop: recorder was built on another env batch")
+        if recorder is not None and train_log is not None:
+            raise ValueError("RoundLoop: train_log empties the episode log every round, the recorder looks ended episodes up in "
+                             "it: not both on one loop")
+        self.recorder = recorder
         if train_log is not None and train_log.venv is not venv:
             raise ValueError("RoundLoop: train_log was built on another env batch")
         self.train_log = train_log
@@ -218,6 +228,7 @@ class RoundLoop:
         venv.reset_device(self.pool, self.supply.first_episode_ids(), None)
         self._bind_plan()
         venv.round_device(self.pool, None, None, self.live, None, first=True)
+        self._launch_recorder()                    # round 0 of every env's first episode
         torch.cuda.synchronize(dev)
 
     def _bind_plan(self):
@@ -240,6 +251,7 @@ class RoundLoop:
             self.venv.round_device(self.pool, self.act, None, self.live, self.table, round_counter=self.rounds,
                                    replay=self.replay)
             self._launch_train_log()
+            self._launch_recorder()
             return
         # forward + fused argmax / eps-greedy (the dueling tail writes the action next to the logits)
         # (integer_features: the obs rows are the env kernel's own -> encoder / conv1 projections per feature tuple)
@@ -250,6 +262,12 @@ class RoundLoop:
         self.venv.round_device(self.pool, self.act, self.offsets, self.live, self.table, round_counter=self.rounds,
                                replay=self.replay)
         self._launch_train_log()
+        self._launch_recorder()
+
+    def _launch_recorder(self):
+        """The state the round just left, into the per-round curves and traces."""
+        if self.recorder is not None:
+            self.recorder.launch()
 
     def _launch_train_log(self):
         """The episodes the round just ended, into the training log (with the eps the round was played at)."""
@@ -592,8 +610,8 @@ class Collector:
 
     def __init__(self, policy, venv: HipGraphVectorEnv, episodes_per_env: int = 16, seed: int = 0, eps: float = 0.0,
                  replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True,
-                 episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes"):
-        """``episode_stream`` / ``ring``: the episode supply, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
+                 episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes", recorder=None):
+        """``episode_stream`` / ``ring`` / ``recorder``: the episode supply and the per-round recorder, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
         collect result summarises - ``"episodes"``: the final ``logger_stats`` row of each finished episode; ``"steps"``: the
         ``logger_stats`` of every env step played during the call, as the reference pools them
         (multi_agent_collector.py:276,316-322), accumulated by the env kernels (``HipGraphVectorEnv.enable_step_stats``)."""
@@ -604,7 +622,7 @@ class Collector:
         if stats == "steps":
             venv.enable_step_stats()            # before the loop: its `first` launch and every capture see the pool
         self.loop = RoundLoop(venv, policy, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=replay,
-                              use_graph=use_graph, episode_stream=episode_stream, ring=ring)
+                              use_graph=use_graph, episode_stream=episode_stream, ring=ring, recorder=recorder)
         self._decisions = self.loop.counters()["decisions"]
         self.collect_step, self.collect_episode, self.collect_time = 0, 0, 0.0
 
@@ -659,7 +677,7 @@ test_shares.__test__ = False           # (a helper, whatever the name says to py
 
 
 def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float = 0.0, seed: int = 0, use_graph: bool = True,
-                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None):
+                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None, recorder=None):
     """One pass over the evaluation schedule with all envs of ``venv`` at once: ``venv`` is built with ``is_testing=True,
     num_test_episodes=n_episode, spread_test_episodes=True``, so env b owns the list positions ``b, b + B, ...``
     (:func:`test_shares`; envs beyond the list own none).  The episodes come from the device sampler
@@ -670,7 +688,12 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
 
     -> (:class:`CollectStatsWithInfo` with ``returns`` / ``lens`` / ``episode_info`` in list-position order, positions).
     ``n_collected_steps`` counts every decision taken, the surplus episodes' included.  The loop is built with ``eps`` and
-    used once; calling again on the same ``venv`` starts again from the top of the list."""
+    used once; calling again on the same ``venv`` starts again from the top of the list.
+
+    ``recorder`` (:class:`melissa_amd.round_record.RoundRecorder` on ``venv``): reset here, given the shares as its quota - so
+    the surplus episodes stay out of its curves and traces too - and launched behind every round; its traces are drained after
+    every chunk, where this loop synchronises anyway (read the result with ``recorder.curves()`` / ``recorder.drain_traces()``).
+    A ring of fewer than ``2 * chunk`` trace records could be overrun between two drains: ValueError."""
     import time
     kw, B, T = venv._sampler_kw, venv.env_num, int(n_episode)
     if not kw["is_testing"] or int(kw["num_test_episodes"]) != T:
@@ -680,13 +703,24 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     shares = np.asarray(test_shares(T, B))
     capacity = int(log_capacity) if log_capacity is not None else max(1024, 16 * (T + B))
     t0 = time.perf_counter()
+    if recorder is not None:
+        if recorder.venv is not venv:
+            raise ValueError("evaluate_spread: recorder was built on another env batch")
+        if recorder.trace_envs and recorder.trace_capacity < 2 * int(chunk):
+            raise ValueError(f"evaluate_spread: trace_capacity={recorder.trace_capacity} is below twice the {int(chunk)} rounds "
+                             f"played between two drains of the traces")
     venv.scalars().zero_()                     # the episode cursors count from 0 again: this pass starts at the top
+    if recorder is not None:
+        recorder.reset()
+        recorder.set_quota(shares)
     col = Collector(policy, venv, seed=seed, eps=eps, chunk=chunk, use_graph=use_graph, log_capacity=capacity,
-                    episode_stream="test", ring=ring)
+                    episode_stream="test", ring=ring, recorder=recorder)
     with torch.no_grad():
         while True:
             col.loop.run(col.chunk)
             sc = venv.scalars().cpu().numpy()                                     # synchronises
+            if recorder is not None:
+                recorder.drain_traces()
             errors = int(np.bitwise_or.reduce(sc[:, _lib.S_ERROR]))
             if errors:
                 raise RuntimeError(f"env error flags {errors:#x} (episode pool exhausted or desynchronised actions)")

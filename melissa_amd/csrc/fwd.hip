@@ -876,6 +876,7 @@ size_t mel_abi_sizeof(int32_t which) {
         case 12: return sizeof(mel_adam_tensors);
         case 13: return sizeof(mel_replay_priority);
         case 14: return sizeof(mel_train_log);
+        case 15: return sizeof(mel_round_record);
         default: return 0;
     }
 }

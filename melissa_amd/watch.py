@@ -13,6 +13,12 @@ the device and replayed from a HIP graph (:func:`melissa_amd.collect.evaluate_sp
 the policy saw, what it did and the convolutions' attention weights - which neighbours each node listened to - into an
 ``.npz`` (:func:`record_attention`); the evaluation and its printed result are the same with and without it.
 
+``--curves-out FILE``, ``--trace-out FILE [--trace-envs K]`` and ``--render-out DIR`` (all with ``--spread``) record the
+evaluation round by round on the device (:class:`melissa_amd.round_record.RoundRecorder`): the dissemination curves - coverage
+and messages against the round, delivery delay - as JSON, the per-node state of envs ``0 .. K-1`` after every round as an
+``.npz``, and one SVG per round and episode coloured by the reference's ``draw_graph`` rule (:mod:`melissa_amd.render`).  The
+printed result is the same with and without them.
+
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
 ``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by ``python -m melissa_amd.train --epoch ...``
 (``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth``) or by the reference's trainer (keys ``model.*`` /
@@ -30,6 +36,7 @@ import torch
 from .collect import Collector, RoundLoop, evaluate_spread
 from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
+from .round_record import check_record_args
 from .train import AGGREGATORS, N_DGN_NETWORK, build_network, check_network_args, load_policy_weights
 
 
@@ -67,7 +74,8 @@ def record_attention(policy, venv, rounds: int, seed: int = 0) -> dict:
 def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=None, seed=9, device="cuda:0",
           dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
           graphs=16, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
-          aggregator_function="max", attention_out=None, attention_rounds=8):
+          aggregator_function="max", attention_out=None, attention_rounds=8, curves_out=None, trace_out=None, trace_envs=1,
+          render_out=None):
     """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
     random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
     ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
@@ -77,7 +85,12 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     trained at another shape is a ValueError naming the mismatching key and both shapes.
     ``attention_out``: path of an ``.npz`` that receives :func:`record_attention` of ``attention_rounds`` greedy rounds on a
     separate batch of ``min(envs, 4)`` envs (every env walks the test list from the top, ``spread`` or not), played after the
-    evaluation: the returned dict is the same with and without it."""
+    evaluation: the returned dict is the same with and without it.
+    ``curves_out`` (a JSON file: :func:`melissa_amd.round_record.summarise` of the evaluation's episodes plus the raw ``running``
+    / ``ended`` sums and the recorder's counters), ``trace_out`` (an ``.npz``: the per-node state of envs ``0 .. trace_envs - 1``
+    after every round of their episodes) and ``render_out`` (a directory: one SVG per round of those episodes) need ``spread``:
+    the recorder rides behind the spread evaluation's rounds and leaves the returned dict as it is."""
+    check_record_args(spread, curves_out, trace_out, render_out, trace_envs)
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function,
                        feature_dtype=feature_dtype)
     if spread and collect_stats != "episodes":
@@ -100,13 +113,20 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     venv = HipGraphVectorEnv(envs, n_nodes, graph_pool=pool, dynamic_graph=dynamic_graph, device=device, max_moves=64,
                              seed=seed, construct_like_reference=False, is_testing=True, num_test_episodes=episodes,
                              scripted_agents_ratio=scripted_agents_ratio, heuristic=heuristic, spread_test_episodes=spread)
+    recorder = None
+    if curves_out is not None or trace_out is not None or render_out is not None:
+        from .round_record import RoundRecorder
+        traced = range(min(int(trace_envs), envs)) if (trace_out is not None or render_out is not None) else ()
+        recorder = RoundRecorder(venv, trace_envs=traced, trace_capacity=64)
     if spread:
-        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed)
+        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed, recorder=recorder)
     else:
         per_env = -(-episodes // envs) + 2
         col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64,
                         stats=collect_stats)
         out = col.collect(n_episode=episodes)
+    if recorder is not None:
+        write_record(recorder, n_nodes, curves_out, trace_out, render_out)
     if attention_out is not None:
         # AFTER the evaluation and on an env batch of its own (built like the evaluation's: same pool, seed and flags), so the
         # result below is what it is without the flag
@@ -120,6 +140,27 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     keys = ["n/ep", "n/st", "collect_time", "collect_speed"] + (["rew", "len"] if out.returns_stat is not None else []) \
         + list(out.info.stats) + (["n_info_rows"] if collect_stats == "steps" else [])
     return {k: out[k] for k in keys}
+
+
+def write_record(recorder, n_nodes: int, curves_out=None, trace_out=None, render_out=None) -> None:
+    """What the recorder holds after an evaluation, into the files the caller asked for."""
+    from .render import write_svg_frames
+    from .round_record import save_traces, summarise
+    running, ended, counters = recorder.curves()
+    traces, lost = recorder.drain_traces()
+    if curves_out is not None:
+        summary = summarise(running, ended, n_nodes=n_nodes)
+        doc = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in summary.items() if k != "delay"}
+        doc["delay"] = {str(q): r for q, r in summary["delay"].items()}
+        doc.update(running_sums=running.tolist(), ended_sums=ended.tolist(), counters=dict(counters, lost_trace_records=int(lost)))
+        with open(curves_out, "w") as f:
+            json.dump(doc, f)
+    if trace_out is not None:
+        save_traces(trace_out, traces)
+    if render_out is not None:
+        for episodes in traces.values():
+            for ep in episodes:
+                write_svg_frames(ep, render_out)
 
 
 def arg_parser() -> argparse.ArgumentParser:
@@ -156,7 +197,23 @@ def arg_parser() -> argparse.ArgumentParser:
                          "alpha_conv2: [rounds, envs, N target, N source, heads]) of --attention-rounds greedy rounds on "
                          "min(--envs, 4) envs of their own; the evaluation is unaffected")
     ap.add_argument("--attention-rounds", type=int, default=8, help="rounds recorded into --attention-out")
+    # (absent from the namespace unless given: callers that compare the namespace of a plain call see what they saw)
+    ap.add_argument("--curves-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help="JSON file that receives the evaluation's per-round curves (coverage, messages, delivery delay); "
+                         "needs --spread")
+    ap.add_argument("--trace-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help=".npz that receives the per-node state of the traced envs after every round; needs --spread")
+    ap.add_argument("--trace-envs", type=int, default=argparse.SUPPRESS,
+                    help="envs 0 .. K-1 are traced for --trace-out / --render-out (default 1)")
+    ap.add_argument("--render-out", default=argparse.SUPPRESS, metavar="DIR",
+                    help="directory that receives one SVG per round of the traced envs' episodes; needs --spread")
     return ap
+
+
+def record_args(a: argparse.Namespace) -> tuple:
+    """(curves_out, trace_out, render_out, trace_envs) of a parsed command line, with their defaults where not given."""
+    return (getattr(a, "curves_out", None), getattr(a, "trace_out", None), getattr(a, "render_out", None),
+            int(getattr(a, "trace_envs", 1)))
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -171,6 +228,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--collect-stats steps is not offered with --spread (surplus episodes would enter the pool)")
     if a.attention_rounds < 1:
         ap.error("--attention-rounds: at least one round")
+    try:
+        check_record_args(a.spread, *record_args(a))
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 
@@ -185,7 +246,8 @@ def main(argv=None):
                            graph_pool=a.graph_pool, graphs=a.graphs, hidden_emb=a.hidden_emb, num_heads=a.num_heads,
                            dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
                            dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
-                           attention_out=a.attention_out, attention_rounds=a.attention_rounds)))
+                           attention_out=a.attention_out, attention_rounds=a.attention_rounds,
+                           **dict(zip(("curves_out", "trace_out", "render_out", "trace_envs"), record_args(a))))))
 
 
 if __name__ == "__main__":
