@@ -1126,6 +1126,84 @@ mel_status mel_round_record_round(const mel_round_record* rec, const mel_env_bat
 mel_status mel_round_record_read(const mel_round_record* rec, double* running_out, double* ended_out, int64_t* counters_out,
                                  void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The policy's decisions per round, recorded ON THE DEVICE: which nodes the policy let relay, how sure it was, against the
+ * round index and against the node's degree (the forwarding ratio per hop and per neighbourhood size of a dissemination
+ * paper).  The data exists between two launches only: mel_*_forward_agents / mel_hldgn_forward_envs_select writes the round's
+ * logits and actions, mel_env_round consumes the actions and overwrites `live`.  So ONE capturable launch sits BETWEEN the
+ * forward and mel_env_round and reads what the forward wrote and the state the decisions were taken in.  It touches nothing
+ * the round loop reads (not the episode log either: it rides with or without mel_round_record / mel_train_log).
+ * All pointers of mel_decision_record are caller-owned DEVICE memory (B = n_envs, R = max_rounds, D = n_degrees, N = n_nodes,
+ * W = MEL_SET_WORDS(N)):
+ *   by_round   double [B][R][MEL_DR_FIELDS]  sums over the decisions env b took in a state with MEL_S_NUM_MOVES == r  (start: 0)
+ *   by_degree  double [B][D][MEL_DR_FIELDS]  the same rows by the deciding node's degree, min(degree, D - 1)          (start: 0)
+ *   overflow   int64  [B]   by_round rows dropped because their round index was >= R (by_degree is still booked)      (start: 0)
+ *   skipped    int64  [B]   launches that found the env with MEL_S_ERROR != 0                                         (start: 0)
+ *   quota      int32  [B]   optional (NULL: no limit): episodes of env b that count (mel_round_record's rule)
+ * mel_decision_record_round(rec, env, logits, act, row_offsets, live, n_actions, stream): logits / act / row_offsets / live are
+ * the round's forward outputs in one of the two layouts of the round loop -
+ *   row_offsets != NULL (L-DGN, DGN-R): the rows of env b are row_offsets[b] .. row_offsets[b + 1], one per member of live[b]
+ *     in ascending node id; logits float [rows][2], act int32 [rows];
+ *   row_offsets == NULL (HL-DGN): logits row b serves every agent of live[b]; act is the dense int32 [B][N] layout;
+ *   live uint64 [B][W] (members >= N are ignored).  n_actions must be 2 ("relay" is action 1), else MEL_ERR_UNSUPPORTED.
+ * Per env (one wavefront, 4 envs per 256-lane workgroup, no atomics - an env owns its rows):
+ *   - MEL_S_ERROR != 0: skipped[b] += 1, nothing else;
+ *   - quota && MEL_S_EPISODES_DONE >= quota[b]: nothing;
+ *   - the policy's decisions are the members of live[b] that are not in MEL_SET_SCRIPTED (a scripted node's action is replaced
+ *     by its heuristic inside the env).  For each, in ASCENDING node id, one after the other, a row of MEL_DR_FIELDS doubles is
+ *     added to by_round[b][r], r = MEL_S_NUM_MOVES, and to by_degree[b][min(degree, D - 1)], degree = column 2 of the node's
+ *     obs_matrix row (q = the node's logits row, a = its action):
+ *       0 decisions: 1;  1 relays: a == 1;  2 gap = q[1] - q[0], ONE fp32 subtraction, widened;  3 gap * gap in double;
+ *       4 the chosen action's Q (q[1] when a == 1, else q[0]);  5 the row's larger Q (q[1] when q[1] > q[0], else q[0]);
+ *       6 non-greedy: a differs from the first maximum of q, which is what the fused selection takes at eps = 0;
+ *       7 first decisions: the node's MEL_SEL_TAKEN_ACTION bit is clear.
+ *     The fixed order makes the floating fields reproducible bit for bit;
+ *   - r >= R: the decision's by_round row is dropped and overflow[b] += 1 (per dropped row); its by_degree row is still booked;
+ *   - trace sink (n_trace > 0): trace_env[t] lists up to MEL_DR_MAX_TRACE distinct envs (VALUES inside the struct, checked on the
+ *     host), each with a ring of trace_capacity records.  A launch that booked at least one decision for a listed env writes
+ *     record trace_cursor[t] % trace_capacity and advances trace_cursor[t] (int64, start: 0); rec = t * trace_capacity + slot:
+ *       trace_meta  int32  [T][cap][8]     env, episode ordinal (episodes_done), MEL_S_EPISODE, num_moves, decisions, relays, 0, 0
+ *       trace_sets  uint64 [T][cap][2][W]  the deciding set, the relaying set (deciding with a == 1)
+ *       trace_q     float  [T][cap][N][2]  the node's logits row; 0 for nodes that did not decide
+ *     Records join mel_round_record's node traces on (env, episode ordinal, num_moves): the state sampled after round r - 1 is
+ *     the state round r's decisions were taken in.
+ * mel_decision_record_read: by_round_out device double [R][MEL_DR_FIELDS], by_degree_out device double [D][MEL_DR_FIELDS] = the
+ *   envs' rows added in ascending env order (a thread per (row, field): equal inputs give equal bits), counters_out device
+ *   int64 [4] = MEL_DRC_*: the sums of overflow and skipped, two reserved (written 0).
+ * Neither reads on the host nor allocates: both replay from a HIP graph.  MEL_ERR_INVALID_ARG: a null record / buffer / env /
+ * logits / act / live / output, an unbound env batch, n_envs or n_nodes other than the env batch's, max_rounds outside
+ * [1, MEL_DR_MAX_ROUNDS], n_degrees outside [1, MEL_DR_MAX_DEGREES], n_trace outside [0, MEL_DR_MAX_TRACE], a traced env
+ * outside [0, n_envs) or listed twice, trace_capacity < 1 or a null trace buffer with n_trace > 0. */
+#define MEL_DR_FIELDS       8
+#define MEL_DR_MAX_TRACE   16
+#define MEL_DR_MAX_ROUNDS  (1 << 20)
+#define MEL_DR_MAX_DEGREES MEL_MAX_NODES
+#define MEL_DRC_OVERFLOW    0
+#define MEL_DRC_SKIPPED     1
+typedef struct mel_decision_record {
+    double*        by_round;
+    double*        by_degree;
+    int64_t*       overflow;
+    int64_t*       skipped;
+    const int32_t* quota;
+    int64_t*       trace_cursor;
+    int32_t*       trace_meta;
+    uint64_t*      trace_sets;
+    float*         trace_q;
+    int32_t        n_envs;
+    int32_t        n_nodes;
+    int32_t        max_rounds;
+    int32_t        n_degrees;
+    int32_t        n_trace;
+    int32_t        trace_capacity;
+    int32_t        trace_env[MEL_DR_MAX_TRACE];
+} mel_decision_record;
+mel_status mel_decision_record_round(const mel_decision_record* rec, const mel_env_batch* env, const float* logits,
+                                     const int32_t* act, const int32_t* row_offsets, const uint64_t* live, int32_t n_actions,
+                                     void* stream);
+mel_status mel_decision_record_read(const mel_decision_record* rec, double* by_round_out, double* by_degree_out,
+                                    int64_t* counters_out, void* stream);
+
 /* last() only (mutates is_new_round exactly like GraphEnv.observe, graph.py:205-211). */
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n,
                            const mel_env_obs* out, void* stream);
@@ -1163,7 +1241,7 @@ const char* mel_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, for binding authors to check their mirrors
  * against: which = 0 mel_linear, 1 mel_gatv2, 2 mel_mlp, 3 mel_weights, 4 mel_select, 5 mel_env_batch,
  * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors,
- * 13 mel_replay_priority, 14 mel_train_log, 15 mel_round_record;
+ * 13 mel_replay_priority, 14 mel_train_log, 15 mel_round_record, 16 mel_decision_record;
  * 0 for anything else. */
 size_t mel_abi_sizeof(int32_t which);
 const char* mel_version(void);

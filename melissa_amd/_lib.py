@@ -44,7 +44,8 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_env_observe", "mel_env_round", "mel_prof_create", "mel_prof_destroy", "mel_prof_attach", "mel_prof_reset",
            "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
            "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate", "mel_train_log_scratch_bytes",
-           "mel_train_log_round", "mel_train_log_update", "mel_round_record_round", "mel_round_record_read")
+           "mel_train_log_round", "mel_train_log_update", "mel_round_record_round", "mel_round_record_read",
+           "mel_decision_record_round", "mel_decision_record_read")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -140,6 +141,21 @@ class MelRoundRecord(C.Structure):
                 ("trace_agent_msgs", C.c_void_p), ("trace_received", C.c_void_p), ("n_envs", C.c_int32), ("n_nodes", C.c_int32),
                 ("max_rounds", C.c_int32), ("n_trace", C.c_int32), ("trace_capacity", C.c_int32), ("reserved", C.c_int32),
                 ("trace_env", C.c_int32 * RR_MAX_TRACE)]
+
+
+# mel_decision_record: the row layout (MEL_DR_*), the read counters (MEL_DRC_*) and the struct
+DR_FIELDS, DR_MAX_TRACE, DR_MAX_ROUNDS, DR_MAX_DEGREES = 8, 16, 1 << 20, MAX_NODES
+(DR_DECISIONS, DR_RELAYS, DR_GAP, DR_GAP_SQ, DR_CHOSEN_Q, DR_MAX_Q, DR_NON_GREEDY, DR_FIRST) = range(8)
+DRC_OVERFLOW, DRC_SKIPPED = 0, 1
+DR_TRACE_SETS = ("deciding", "relaying")
+
+
+class MelDecisionRecord(C.Structure):
+    _fields_ = [("by_round", C.c_void_p), ("by_degree", C.c_void_p), ("overflow", C.c_void_p), ("skipped", C.c_void_p),
+                ("quota", C.c_void_p), ("trace_cursor", C.c_void_p), ("trace_meta", C.c_void_p), ("trace_sets", C.c_void_p),
+                ("trace_q", C.c_void_p), ("n_envs", C.c_int32), ("n_nodes", C.c_int32), ("max_rounds", C.c_int32),
+                ("n_degrees", C.c_int32), ("n_trace", C.c_int32), ("trace_capacity", C.c_int32),
+                ("trace_env", C.c_int32 * DR_MAX_TRACE)]
 
 
 class MelEnvBatch(C.Structure):
@@ -317,6 +333,10 @@ def load(build_if_missing: bool = True):
     lib.mel_round_record_round.argtypes = [C.POINTER(MelRoundRecord), E, vp]
     lib.mel_round_record_read.restype = i32
     lib.mel_round_record_read.argtypes = [C.POINTER(MelRoundRecord), vp, vp, vp, vp]
+    lib.mel_decision_record_round.restype = i32
+    lib.mel_decision_record_round.argtypes = [C.POINTER(MelDecisionRecord), E, vp, vp, vp, vp, i32, vp]
+    lib.mel_decision_record_read.restype = i32
+    lib.mel_decision_record_read.argtypes = [C.POINTER(MelDecisionRecord), vp, vp, vp, vp]
     lib.mel_mpr_sets.restype = i32
     lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz

@@ -146,7 +146,7 @@ class RoundLoop:
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
                  stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: "bool | str | None" = None,
                  ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None,
-                 train_log=None, recorder=None):
+                 train_log=None, recorder=None, decisions=None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
         ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes;
@@ -161,8 +161,15 @@ class RoundLoop:
         ``recorder`` (:class:`melissa_amd.round_record.RoundRecorder` on ``venv``): every round, eager or captured, is followed
         by ``mel_round_record_round``, which samples the state the round left into the recorder's per-round curves and traces;
         one more launch behind the constructor's ``first`` launch records the first episodes' round 0.  None (the default): no
-        such launch, the sequence is the one without the recorder."""
+        such launch, the sequence is the one without the recorder.
+        ``decisions`` (:class:`melissa_amd.decision_record.DecisionRecorder` on ``venv``): every round, eager or captured, issues
+        ``mel_decision_record_round`` BETWEEN the forward and ``mel_env_round`` - the only place where the round's logits, actions
+        and ``live`` sets exist together - which books the policy's decisions by round index and by node degree.  It does not
+        touch the episode log: with or without ``recorder`` / ``train_log``.  None (the default): no such launch."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
+        if decisions is not None and decisions.venv is not venv:
+            raise ValueError("RoundLoop: decisions was built on another env batch")
+        self.decisions = decisions
         if recorder is not None and recorder.venv is not venv:
             raise ValueError("RoundLoop: recorder was built on another env batch")
         if recorder is not None and train_log is not None:
@@ -247,6 +254,7 @@ class RoundLoop:
             # mel_select_action_envs)
             net.hip_forward_envs(self._obs_matrix, out=self.logits, workspace=self.workspace, select=self._select,
                                  plan_ready=True, integer_features=self.integer_features)
+            self._launch_decisions(None)
             self._bind_plan()
             self.venv.round_device(self.pool, self.act, None, self.live, self.table, round_counter=self.rounds,
                                    replay=self.replay)
@@ -258,11 +266,17 @@ class RoundLoop:
         net.hip_forward_agents(self._obs_matrix, self.live, self.rows_cap, out=self.logits, row_offsets=self.offsets,
                                select=self._select, workspace=self.workspace, plan_ready=True,
                                integer_features=self.integer_features)
+        self._launch_decisions(self.offsets)
         self._bind_plan()
         self.venv.round_device(self.pool, self.act, self.offsets, self.live, self.table, round_counter=self.rounds,
                                replay=self.replay)
         self._launch_train_log()
         self._launch_recorder()
+
+    def _launch_decisions(self, offsets):
+        """What the forward just decided, with the state it decided in, into the decision tables and traces."""
+        if self.decisions is not None:
+            self.decisions.launch(self.logits, self.act, offsets, self.live)
 
     def _launch_recorder(self):
         """The state the round just left, into the per-round curves and traces."""
@@ -610,8 +624,9 @@ class Collector:
 
     def __init__(self, policy, venv: HipGraphVectorEnv, episodes_per_env: int = 16, seed: int = 0, eps: float = 0.0,
                  replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True,
-                 episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes", recorder=None):
-        """``episode_stream`` / ``ring`` / ``recorder``: the episode supply and the per-round recorder, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
+                 episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes", recorder=None,
+                 decisions=None):
+        """``episode_stream`` / ``ring`` / ``recorder`` / ``decisions``: the episode supply, the per-round recorder and the decision recorder, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
         collect result summarises - ``"episodes"``: the final ``logger_stats`` row of each finished episode; ``"steps"``: the
         ``logger_stats`` of every env step played during the call, as the reference pools them
         (multi_agent_collector.py:276,316-322), accumulated by the env kernels (``HipGraphVectorEnv.enable_step_stats``)."""
@@ -622,7 +637,8 @@ class Collector:
         if stats == "steps":
             venv.enable_step_stats()            # before the loop: its `first` launch and every capture see the pool
         self.loop = RoundLoop(venv, policy, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=replay,
-                              use_graph=use_graph, episode_stream=episode_stream, ring=ring, recorder=recorder)
+                              use_graph=use_graph, episode_stream=episode_stream, ring=ring, recorder=recorder,
+                              decisions=decisions)
         self._decisions = self.loop.counters()["decisions"]
         self.collect_step, self.collect_episode, self.collect_time = 0, 0, 0.0
 
@@ -677,7 +693,7 @@ test_shares.__test__ = False           # (a helper, whatever the name says to py
 
 
 def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float = 0.0, seed: int = 0, use_graph: bool = True,
-                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None, recorder=None):
+                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None, recorder=None, decisions=None):
     """One pass over the evaluation schedule with all envs of ``venv`` at once: ``venv`` is built with ``is_testing=True,
     num_test_episodes=n_episode, spread_test_episodes=True``, so env b owns the list positions ``b, b + B, ...``
     (:func:`test_shares`; envs beyond the list own none).  The episodes come from the device sampler
@@ -693,7 +709,10 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     ``recorder`` (:class:`melissa_amd.round_record.RoundRecorder` on ``venv``): reset here, given the shares as its quota - so
     the surplus episodes stay out of its curves and traces too - and launched behind every round; its traces are drained after
     every chunk, where this loop synchronises anyway (read the result with ``recorder.curves()`` / ``recorder.drain_traces()``).
-    A ring of fewer than ``2 * chunk`` trace records could be overrun between two drains: ValueError."""
+    A ring of fewer than ``2 * chunk`` trace records could be overrun between two drains: ValueError.
+    ``decisions`` (:class:`melissa_amd.decision_record.DecisionRecorder` on ``venv``): the same - reset, the shares as its quota,
+    launched between every round's forward and env launch, drained after every chunk (``decisions.tables()`` /
+    ``decisions.drain_traces()``)."""
     import time
     kw, B, T = venv._sampler_kw, venv.env_num, int(n_episode)
     if not kw["is_testing"] or int(kw["num_test_episodes"]) != T:
@@ -703,24 +722,27 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     shares = np.asarray(test_shares(T, B))
     capacity = int(log_capacity) if log_capacity is not None else max(1024, 16 * (T + B))
     t0 = time.perf_counter()
-    if recorder is not None:
-        if recorder.venv is not venv:
-            raise ValueError("evaluate_spread: recorder was built on another env batch")
-        if recorder.trace_envs and recorder.trace_capacity < 2 * int(chunk):
-            raise ValueError(f"evaluate_spread: trace_capacity={recorder.trace_capacity} is below twice the {int(chunk)} rounds "
-                             f"played between two drains of the traces")
+    for name, rec in (("recorder", recorder), ("decisions", decisions)):
+        if rec is not None:
+            if rec.venv is not venv:
+                raise ValueError(f"evaluate_spread: {name} was built on another env batch")
+            if rec.trace_envs and rec.trace_capacity < 2 * int(chunk):
+                raise ValueError(f"evaluate_spread: trace_capacity={rec.trace_capacity} is below twice the {int(chunk)} rounds "
+                                 f"played between two drains of the traces")
     venv.scalars().zero_()                     # the episode cursors count from 0 again: this pass starts at the top
-    if recorder is not None:
-        recorder.reset()
-        recorder.set_quota(shares)
+    for rec in (recorder, decisions):
+        if rec is not None:
+            rec.reset()
+            rec.set_quota(shares)
     col = Collector(policy, venv, seed=seed, eps=eps, chunk=chunk, use_graph=use_graph, log_capacity=capacity,
-                    episode_stream="test", ring=ring, recorder=recorder)
+                    episode_stream="test", ring=ring, recorder=recorder, decisions=decisions)
     with torch.no_grad():
         while True:
             col.loop.run(col.chunk)
             sc = venv.scalars().cpu().numpy()                                     # synchronises
-            if recorder is not None:
-                recorder.drain_traces()
+            for rec in (recorder, decisions):
+                if rec is not None:
+                    rec.drain_traces()
             errors = int(np.bitwise_or.reduce(sc[:, _lib.S_ERROR]))
             if errors:
                 raise RuntimeError(f"env error flags {errors:#x} (episode pool exhausted or desynchronised actions)")

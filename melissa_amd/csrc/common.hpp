@@ -152,6 +152,17 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int src) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// the greedy action of a row of dueling-combined values q[a] - mean + v: the FIRST maximum, as argmax.  What every fused
+// selection takes at eps = 0 (heads.hpp) and what the decision recorder calls "greedy" (decision_record.hpp): one rule for ties
+__device__ __forceinline__ int greedy_action(const float (&q)[8], float mean, float v, int na) {
+    int best = 0;
+    float bv = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+        if (a < na && q[a] - mean + v > bv) bv = q[a] - mean + v, best = a;
+    return best;
+}
+
 // ---- cross-lane reads with a WAVE-UNIFORM source lane: v_readlane (VALU -> SGPR), no LDS round trip ----
 __device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {

@@ -1495,3 +1495,4 @@ mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n
 
 #include "train_log.hpp"      // mel_train_log_round / mel_train_log_update: training curves summed per interval on the device
 #include "round_record.hpp"   // mel_round_record_round / mel_round_record_read: per-round curves and traces of an evaluation
+#include "decision_record.hpp"   // mel_decision_record_round / mel_decision_record_read: the policy's decisions per round and degree

@@ -877,6 +877,7 @@ size_t mel_abi_sizeof(int32_t which) {
         case 13: return sizeof(mel_replay_priority);
         case 14: return sizeof(mel_train_log);
         case 15: return sizeof(mel_round_record);
+        case 16: return sizeof(mel_decision_record);
         default: return 0;
     }
 }

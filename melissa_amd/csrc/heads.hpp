@@ -24,17 +24,14 @@ __device__ __forceinline__ float sel_eps(const mel_select& sel) { return sel.eps
 
 // fused DQN action selection of row b from its dueling-combined values q[a] - mean + v
 __device__ __forceinline__ void select_fused(const float (&q)[8], float mean, float v, int na, const mel_select& sel, int b) {
-    int best = 0;
-    float bv = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-        if (a < na && q[a] - mean + v > bv) bv = q[a] - mean + v, best = a;
+    int best = greedy_action(q, mean, v, na);
     const float eps = sel_eps(sel);
     if (eps > 0.f) {
         const uint32_t step = sel.step_dev ? *sel.step_dev : 0u;
         const uint32_t base = mix32(sel.seed ^ mix32(step * 0x9e3779b9U + (uint32_t)b));
         if (u01(base) < eps) {
-            best = 0, bv = -1.f;
+            float bv = -1.f;
+            best = 0;
             for (int a = 0; a < na; ++a) {
                 const float u = u01(mix32(base + 0x85ebca6bU * (uint32_t)(a + 1)));
                 if (u > bv) bv = u, best = a;
@@ -54,17 +51,14 @@ __device__ __forceinline__ uint32_t env_agent_key(long b, int n_nodes, int i) {
 }
 __device__ __forceinline__ void select_env_agent(const float (&q)[8], float mean, float v, int na, const mel_select& sel,
                                                  int b, int i) {
-    int best = 0;
-    float bv = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-        if (a < na && q[a] - mean + v > bv) bv = q[a] - mean + v, best = a;
+    int best = greedy_action(q, mean, v, na);
     const float eps = sel_eps(sel);
     if (eps > 0.f) {
         const uint32_t step = sel.step_dev ? *sel.step_dev : 0u;
         const uint32_t base = mix32(sel.seed ^ mix32(step * 0x9e3779b9U + env_agent_key(b, sel.n_nodes, i)));
         if (u01(base) < eps) {
-            best = 0, bv = -1.f;
+            float bv = -1.f;
+            best = 0;
             for (int a = 0; a < na; ++a) {
                 const float u = u01(mix32(base + 0x85ebca6bU * (uint32_t)(a + 1)));
                 if (u > bv) bv = u, best = a;

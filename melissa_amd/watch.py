@@ -19,6 +19,12 @@ and messages against the round, delivery delay - as JSON, the per-node state of 
 ``.npz``, and one SVG per round and episode coloured by the reference's ``draw_graph`` rule (:mod:`melissa_amd.render`).  The
 printed result is the same with and without them.
 
+``--decisions-out FILE`` and ``--decision-trace-out FILE [--trace-envs K]`` (with ``--spread``) record the policy's decisions
+between every round's forward and env launch (:class:`melissa_amd.decision_record.DecisionRecorder`): relay rate, Q gap,
+non-greedy and first-decision shares against the round index and against the node's degree as JSON, and per round of envs
+``0 .. K-1`` who decided, who relayed and with which Q values as an ``.npz`` that joins ``--trace-out`` on
+(env, episode ordinal, round).
+
 Graphs: connected random geometric graphs (the reference reads graph_topologies/testing_N/*; pass your own pool through
 ``watch(graph_pool=...)``).  ``--load`` takes a state_dict saved by ``python -m melissa_amd.train --epoch ...``
 (``<logdir>/<model>/weights/<model_name>_best.pth`` / ``_last.pth``) or by the reference's trainer (keys ``model.*`` /
@@ -36,6 +42,7 @@ import torch
 from .collect import Collector, RoundLoop, evaluate_spread
 from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
+from .decision_record import check_decision_args
 from .round_record import check_record_args
 from .train import AGGREGATORS, N_DGN_NETWORK, build_network, check_network_args, load_policy_weights
 
@@ -75,7 +82,7 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
           dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
           graphs=16, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
           aggregator_function="max", attention_out=None, attention_rounds=8, curves_out=None, trace_out=None, trace_envs=1,
-          render_out=None):
+          render_out=None, decisions_out=None, decision_trace_out=None):
     """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
     random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
     ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
@@ -89,8 +96,12 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     ``curves_out`` (a JSON file: :func:`melissa_amd.round_record.summarise` of the evaluation's episodes plus the raw ``running``
     / ``ended`` sums and the recorder's counters), ``trace_out`` (an ``.npz``: the per-node state of envs ``0 .. trace_envs - 1``
     after every round of their episodes) and ``render_out`` (a directory: one SVG per round of those episodes) need ``spread``:
-    the recorder rides behind the spread evaluation's rounds and leaves the returned dict as it is."""
+    the recorder rides behind the spread evaluation's rounds and leaves the returned dict as it is.
+    ``decisions_out`` (a JSON file: :func:`melissa_amd.decision_record.summarise_decisions` of the evaluation's decisions plus the
+    raw ``by_round`` / ``by_degree`` sums and the counters) and ``decision_trace_out`` (an ``.npz``: per round of envs
+    ``0 .. trace_envs - 1`` the deciding and relaying sets and the Q values, keyed like ``trace_out``) need ``spread`` too."""
     check_record_args(spread, curves_out, trace_out, render_out, trace_envs)
+    check_decision_args(spread, decisions_out, decision_trace_out, trace_envs)
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function,
                        feature_dtype=feature_dtype)
     if spread and collect_stats != "episodes":
@@ -118,8 +129,13 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         from .round_record import RoundRecorder
         traced = range(min(int(trace_envs), envs)) if (trace_out is not None or render_out is not None) else ()
         recorder = RoundRecorder(venv, trace_envs=traced, trace_capacity=64)
+    decisions = None
+    if decisions_out is not None or decision_trace_out is not None:
+        from .decision_record import DecisionRecorder
+        traced = range(min(int(trace_envs), envs)) if decision_trace_out is not None else ()
+        decisions = DecisionRecorder(venv, trace_envs=traced, trace_capacity=64)
     if spread:
-        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed, recorder=recorder)
+        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed, recorder=recorder, decisions=decisions)
     else:
         per_env = -(-episodes // envs) + 2
         col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64,
@@ -127,6 +143,8 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         out = col.collect(n_episode=episodes)
     if recorder is not None:
         write_record(recorder, n_nodes, curves_out, trace_out, render_out)
+    if decisions is not None:
+        write_decisions(decisions, decisions_out, decision_trace_out)
     if attention_out is not None:
         # AFTER the evaluation and on an env batch of its own (built like the evaluation's: same pool, seed and flags), so the
         # result below is what it is without the flag
@@ -161,6 +179,29 @@ def write_record(recorder, n_nodes: int, curves_out=None, trace_out=None, render
         for episodes in traces.values():
             for ep in episodes:
                 write_svg_frames(ep, render_out)
+
+
+def write_decisions(decisions, decisions_out=None, decision_trace_out=None) -> None:
+    """What the decision recorder holds after an evaluation, into the files the caller asked for."""
+    from .decision_record import save_decision_traces, summarise_decisions
+    by_round, by_degree, counters = decisions.tables()
+    traces, lost = decisions.drain_traces()
+    if decisions_out is not None:
+        def as_json(v):                                  # arrays as lists; NaN (a ratio over no decision) as null
+            if isinstance(v, dict):
+                return {k: as_json(x) for k, x in v.items()}
+            v = v.tolist() if hasattr(v, "tolist") else v
+            if isinstance(v, list):
+                return [as_json(x) for x in v]
+            return None if isinstance(v, float) and v != v else v
+
+        doc = as_json(summarise_decisions(by_round, by_degree))
+        doc.update(by_round_sums=by_round.tolist(), by_degree_sums=by_degree.tolist(),
+                   counters=dict(counters, lost_trace_records=int(lost)))
+        with open(decisions_out, "w") as f:
+            json.dump(doc, f)
+    if decision_trace_out is not None:
+        save_decision_traces(decision_trace_out, traces)
 
 
 def arg_parser() -> argparse.ArgumentParser:
@@ -207,6 +248,12 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="envs 0 .. K-1 are traced for --trace-out / --render-out (default 1)")
     ap.add_argument("--render-out", default=argparse.SUPPRESS, metavar="DIR",
                     help="directory that receives one SVG per round of the traced envs' episodes; needs --spread")
+    ap.add_argument("--decisions-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help="JSON file that receives the policy's decisions per round index and per node degree (relay rate, Q gap, "
+                         "non-greedy and first-decision shares); needs --spread")
+    ap.add_argument("--decision-trace-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help=".npz that receives, per round of the traced envs (--trace-envs), who decided, who relayed and the Q "
+                         "values; needs --spread")
     return ap
 
 
@@ -214,6 +261,11 @@ def record_args(a: argparse.Namespace) -> tuple:
     """(curves_out, trace_out, render_out, trace_envs) of a parsed command line, with their defaults where not given."""
     return (getattr(a, "curves_out", None), getattr(a, "trace_out", None), getattr(a, "render_out", None),
             int(getattr(a, "trace_envs", 1)))
+
+
+def decision_args(a: argparse.Namespace) -> tuple:
+    """(decisions_out, decision_trace_out) of a parsed command line, None where not given."""
+    return getattr(a, "decisions_out", None), getattr(a, "decision_trace_out", None)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -230,6 +282,7 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--attention-rounds: at least one round")
     try:
         check_record_args(a.spread, *record_args(a))
+        check_decision_args(a.spread, *decision_args(a), trace_envs=record_args(a)[3])
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -247,7 +300,8 @@ def main(argv=None):
                            dueling_q_hidden_sizes=list(a.dueling_q_hidden_sizes),
                            dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
                            attention_out=a.attention_out, attention_rounds=a.attention_rounds,
-                           **dict(zip(("curves_out", "trace_out", "render_out", "trace_envs"), record_args(a))))))
+                           **dict(zip(("curves_out", "trace_out", "render_out", "trace_envs"), record_args(a))),
+                           **dict(zip(("decisions_out", "decision_trace_out"), decision_args(a))))))
 
 
 if __name__ == "__main__":
