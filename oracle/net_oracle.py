@@ -111,14 +111,16 @@ def init_weights(model: str, input_dim=5, hidden=128, heads=4, n_actions=2, seed
 # ----------------------------------------------------------------------------------------------
 # N1: unpack (common.py:6-64) and N2: radius adjacency
 # ----------------------------------------------------------------------------------------------
-def unpack_obs(obs, agents_num, input_dim=5):
+def unpack_obs(obs, agents_num, input_dim=5, dtype=torch.float32):
+    """``dtype``: the type of the features and flags the forward computes with.  (The forwards take the graph from the
+    positions in float32 whatever ``dtype`` is.)"""
     if obs.ndim != 2:
         raise ValueError(f"Expected obs to be 2D, but got shape {obs.shape}")
     bs, dim = obs.shape
     expected = agents_num * (input_dim + 3)
     if dim - 1 != expected:
         raise ValueError(f"Expected {expected} feature cols for nodes, got {dim - 1}")
-    node = obs[:, :dim - 1].reshape(bs, agents_num, input_dim + 3).float()
+    node = obs[:, :dim - 1].reshape(bs, agents_num, input_dim + 3).to(dtype)
     pos = node[:, :, :2]
     feats = node[:, :, 2:2 + input_dim]
     dm_mask = node[:, :, -1:]
@@ -176,12 +178,12 @@ def gatv2_edges(sd, prefix, x, adj, heads):
     dst = torch.cat([dst, loops])
     m = F.leaky_relu(x_r[dst] + x_l[src], 0.2)                          # [E, H, C]
     e = (m * sd[f"{prefix}.att"]).sum(dim=-1)                          # [E, H]
-    e_max = torch.full((bs * n, heads), -float("inf")).scatter_reduce(
+    e_max = torch.full((bs * n, heads), -float("inf"), dtype=e.dtype).scatter_reduce(
         0, dst[:, None].expand(-1, heads), e, reduce="amax", include_self=True)
     p = (e - e_max[dst]).exp()
-    denom = torch.zeros(bs * n, heads).index_add_(0, dst, p) + 1e-16
+    denom = torch.zeros(bs * n, heads, dtype=p.dtype).index_add_(0, dst, p) + 1e-16
     alpha = p / denom[dst]
-    out = torch.zeros(bs * n, heads, c).index_add_(0, dst, x_l[src] * alpha[:, :, None])
+    out = torch.zeros(bs * n, heads, c, dtype=x_l.dtype).index_add_(0, dst, x_l[src] * alpha[:, :, None])
     return out.reshape(bs * n, hc) + sd[f"{prefix}.bias"]
 
 
@@ -199,7 +201,7 @@ def gatv2_dense(sd, prefix, x, adj, heads):
     e = e.masked_fill(~mask[..., None], -float("inf"))
     e_max = e.max(dim=2, keepdim=True).values
     p = torch.exp(e - e_max)
-    p = torch.where(mask[..., None], p, torch.zeros(()))
+    p = torch.where(mask[..., None], p, torch.zeros((), dtype=p.dtype))
     alpha = p / (p.sum(dim=2, keepdim=True) + 1e-16)
     out = torch.einsum("bijh,bjhc->bihc", alpha, x_l)
     return out.reshape(bs * n, hc) + sd[f"{prefix}.bias"]
@@ -222,12 +224,12 @@ def transformer_edges(sd, prefix, x, adj, heads):
     src = b_idx * n + j_idx
     dst = b_idx * n + i_idx
     e = (q[dst] * k[src]).sum(dim=-1) / math.sqrt(c)
-    e_max = torch.full((bs * n, heads), -float("inf")).scatter_reduce(
+    e_max = torch.full((bs * n, heads), -float("inf"), dtype=e.dtype).scatter_reduce(
         0, dst[:, None].expand(-1, heads), e, reduce="amax", include_self=True)
     p = (e - e_max[dst]).exp()
-    denom = torch.zeros(bs * n, heads).index_add_(0, dst, p) + 1e-16
+    denom = torch.zeros(bs * n, heads, dtype=p.dtype).index_add_(0, dst, p) + 1e-16
     alpha = p / denom[dst]
-    out = torch.zeros(bs * n, heads, c).index_add_(0, dst, v[src] * alpha[:, :, None])
+    out = torch.zeros(bs * n, heads, c, dtype=v.dtype).index_add_(0, dst, v[src] * alpha[:, :, None])
     return out.reshape(bs * n, hc)
 
 
@@ -241,8 +243,8 @@ def transformer_dense(sd, prefix, x, adj, heads):
     e = torch.einsum("bihc,bjhc->bijh", q, k) / math.sqrt(c)
     e = e.masked_fill(~adj[..., None], -float("inf"))
     e_max = e.max(dim=2, keepdim=True).values
-    e_max = torch.where(torch.isfinite(e_max), e_max, torch.zeros(()))     # isolated targets
-    p = torch.where(adj[..., None], torch.exp(e - e_max), torch.zeros(()))
+    e_max = torch.where(torch.isfinite(e_max), e_max, torch.zeros((), dtype=e.dtype))     # isolated targets
+    p = torch.where(adj[..., None], torch.exp(e - e_max), torch.zeros((), dtype=e.dtype))
     alpha = p / (p.sum(dim=2, keepdim=True) + 1e-16)
     return torch.einsum("bijh,bjhc->bihc", alpha, v).reshape(bs * n, hc)
 
@@ -259,18 +261,36 @@ def _dueling(sd, x):
 
 
 # ----------------------------------------------------------------------------------------------
-# the two forwards
+# the forwards
 # ----------------------------------------------------------------------------------------------
-def ldgn_forward(sd, obs, agents_num, heads=4, formulation="edges", return_intermediates=False):
-    """l_dgn.py:92-151.  obs: float tensor / ndarray [bs, 8N+1] -> logits [bs, n_actions] fp32."""
+def _inputs(sd, obs, agents_num, dtype, rows):
+    """What the three forwards share: the weights in ``dtype`` (float32: the dict itself; float64: features, flags, weights and
+    every intermediate are double, and autograd reaches the caller's leaves through the conversion), the unpacked
+    observations, the adjacency - always from the float32 positions, strict < and the 32 cap: the graph is part of the input,
+    not of the arithmetic - and the rows of the node matrix the logits are for: the index column's, or ``rows`` = (env, agent)
+    pairs, one logits row per pair on env's graph (the agents forward of the round-batched loop)."""
     obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs)
-    pos, feats, dm, g = unpack_obs(obs, agents_num, sd["encoder.model.0.weight"].shape[1])
+    if dtype != torch.float32:
+        sd = {k: v.to(dtype) for k, v in sd.items()}
+    in_dim = sd["encoder.model.0.weight"].shape[1]
+    pos, feats, dm, g = unpack_obs(obs, agents_num, in_dim) if dtype == torch.float32 else unpack_obs(obs, agents_num, in_dim, dtype)
     bs, n = pos.shape[:2]
-    adj = radius_adjacency(pos)
+    adj = radius_adjacency(pos.float())
+    if rows is None:
+        gi = torch.arange(bs) * n + g
+    else:
+        pairs = torch.as_tensor(np.asarray(rows, dtype=np.int64).reshape(-1, 2))
+        gi = pairs[:, 0] * n + pairs[:, 1]
+    return sd, feats, dm, adj, gi, bs, n
+
+
+def ldgn_forward(sd, obs, agents_num, heads=4, formulation="edges", return_intermediates=False, dtype=torch.float32,
+                 rows=None):
+    """l_dgn.py:92-151.  obs: float tensor / ndarray [bs, 8N+1] -> logits [bs, n_actions] in ``dtype``."""
+    sd, feats, dm, adj, gi, bs, n = _inputs(sd, obs, agents_num, dtype, rows)
     gat = _GAT[formulation]
     x = F.relu(_mlp(sd, "encoder", feats.reshape(bs * n, -1), 2))         # :117-118
-    gi = torch.arange(bs) * n + g                                        # :121
-    x_1 = x[gi]
+    x_1 = x[gi]                                                          # :121
     x = F.relu(gat(sd, "conv1", x, adj, heads))                          # :125-126
     x_2 = x[gi]                                                          # :127 (before the mask)
     x = x * dm.reshape(bs * n, 1)                                        # :128
@@ -280,38 +300,33 @@ def ldgn_forward(sd, obs, agents_num, heads=4, formulation="edges", return_inter
     x_cat = torch.cat([x_1, x_2, x_3], dim=1)                            # :139
     out = _dueling(sd, x_cat)
     if return_intermediates:
-        return out, dict(adj=adj, x_1=x_1, x_2=x_2, x_3=x_3, h1=h1)
+        return out, dict(adj=adj, x_1=x_1, x_2=x_2, x_3=x_3, h1=h1, x_cat=x_cat)
     return out
 
 
-def dgnr_forward(sd, obs, agents_num, heads=4, formulation="edges", return_intermediates=False):
+def dgnr_forward(sd, obs, agents_num, heads=4, formulation="edges", return_intermediates=False, dtype=torch.float32,
+                 rows=None):
     """dgn_r.py:82-129: same skeleton as L-DGN with TransformerConv layers."""
-    obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs)
-    pos, feats, dm, g = unpack_obs(obs, agents_num, sd["encoder.model.0.weight"].shape[1])
-    bs, n = pos.shape[:2]
-    adj = radius_adjacency(pos)
+    sd, feats, dm, adj, gi, bs, n = _inputs(sd, obs, agents_num, dtype, rows)
     conv = _TCONV[formulation]
     x = F.relu(_mlp(sd, "encoder", feats.reshape(bs * n, -1), 2))         # :97-98
-    gi = torch.arange(bs) * n + g
     x_1 = x[gi]
     x = F.relu(conv(sd, "conv1", x, adj, heads))                         # :104-105
     x_2 = x[gi]
     x = x * dm.reshape(bs * n, 1)                                        # :109
     x = F.relu(conv(sd, "conv2", x, adj, heads))                         # :112-113
     x_3 = x[gi]
-    out = _dueling(sd, torch.cat([x_1, x_2, x_3], dim=1))
+    x_cat = torch.cat([x_1, x_2, x_3], dim=1)
+    out = _dueling(sd, x_cat)
     if return_intermediates:
-        return out, dict(adj=adj, x_1=x_1, x_2=x_2, x_3=x_3)
+        return out, dict(adj=adj, x_1=x_1, x_2=x_2, x_3=x_3, x_cat=x_cat)
     return out
 
 
 def hldgn_forward(sd, obs, agents_num, heads=4, aggregator="max", formulation="edges",
-                  return_intermediates=False):
+                  return_intermediates=False, dtype=torch.float32):
     """hl_dgn.py:82-119."""
-    obs = torch.as_tensor(np.asarray(obs) if not torch.is_tensor(obs) else obs)
-    pos, feats, dm, _g = unpack_obs(obs, agents_num, sd["encoder.model.0.weight"].shape[1])
-    bs, n = pos.shape[:2]
-    adj = radius_adjacency(pos)
+    sd, feats, dm, adj, _gi, bs, n = _inputs(sd, obs, agents_num, dtype, None)
     x = F.relu(_mlp(sd, "encoder", feats.reshape(bs * n, -1), 2))
     x = F.relu(_GAT[formulation](sd, "conv1", x, adj, heads))
     x = (x * dm.reshape(bs * n, 1)).view(bs, n, -1)                      # :105

@@ -9,6 +9,7 @@ from melissa_amd.shapes import head_lanes, hip_shape_supported
 # (hidden, heads) -> does the HIP path run it.  Written out here, not derived from the rule under test.
 SHAPE_TABLE = {(64, 2): True, (64, 4): True, (128, 2): True, (128, 4): True, (256, 2): True, (256, 4): True, (512, 2): True,
                (64, 6): True, (128, 6): True,
+               (64, 8): True, (64, 16): True, (128, 1): True, (128, 8): True, (256, 1): True, (512, 1): True,
                (16, 2): False, (16, 4): False, (16, 6): False, (32, 2): False, (32, 4): False, (32, 6): False,
                (512, 4): False, (256, 6): False}
 
