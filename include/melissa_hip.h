@@ -1159,9 +1159,9 @@ mel_status mel_round_record_read(const mel_round_record* rec, double* running_ou
  *       7 first decisions: the node's MEL_SEL_TAKEN_ACTION bit is clear.
  *     The fixed order makes the floating fields reproducible bit for bit;
  *   - r >= R: the decision's by_round row is dropped and overflow[b] += 1 (per dropped row); its by_degree row is still booked;
- *   - trace sink (n_trace > 0): trace_env[t] lists up to MEL_DR_MAX_TRACE distinct envs (VALUES inside the struct, checked on the
- *     host), each with a ring of trace_capacity records.  A launch that booked at least one decision for a listed env writes
- *     record trace_cursor[t] % trace_capacity and advances trace_cursor[t] (int64, start: 0); rec = t * trace_capacity + slot:
+ *   - trace sink (n_trace > 0): mel_round_record's, rule for rule (one implementation serves both: trace_env[], the rings, the
+ *     cursor, the first four header ints, the argument errors; MEL_DR_MAX_TRACE == MEL_RR_MAX_TRACE).  Here a launch that booked
+ *     at least one decision for a listed env writes the record; rec = t * trace_capacity + slot:
  *       trace_meta  int32  [T][cap][8]     env, episode ordinal (episodes_done), MEL_S_EPISODE, num_moves, decisions, relays, 0, 0
  *       trace_sets  uint64 [T][cap][2][W]  the deciding set, the relaying set (deciding with a == 1)
  *       trace_q     float  [T][cap][N][2]  the node's logits row; 0 for nodes that did not decide

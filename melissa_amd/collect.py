@@ -24,6 +24,7 @@ from . import _lib
 from .env.episodes import EpisodeSampler, pack_episodes
 from .env.stream import make_supply
 from .env.vector_env import HipGraphVectorEnv, ObsBuffers
+from .record_common import check_rides
 
 
 def sample_episode_table(venv: HipGraphVectorEnv, episodes_per_env: int, seed: int = 0):
@@ -167,11 +168,9 @@ class RoundLoop:
         and ``live`` sets exist together - which books the policy's decisions by round index and by node degree.  It does not
         touch the episode log: with or without ``recorder`` / ``train_log``.  None (the default): no such launch."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
-        if decisions is not None and decisions.venv is not venv:
-            raise ValueError("RoundLoop: decisions was built on another env batch")
+        check_rides("RoundLoop", "decisions", decisions, venv)
         self.decisions = decisions
-        if recorder is not None and recorder.venv is not venv:
-            raise ValueError("RoundLoop: recorder was built on another env batch")
+        check_rides("RoundLoop", "recorder", recorder, venv)
         if recorder is not None and train_log is not None:
             raise ValueError("RoundLoop: train_log empties the episode log every round, the recorder looks ended episodes up in "
                              "it: not both on one loop")
@@ -723,12 +722,7 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     capacity = int(log_capacity) if log_capacity is not None else max(1024, 16 * (T + B))
     t0 = time.perf_counter()
     for name, rec in (("recorder", recorder), ("decisions", decisions)):
-        if rec is not None:
-            if rec.venv is not venv:
-                raise ValueError(f"evaluate_spread: {name} was built on another env batch")
-            if rec.trace_envs and rec.trace_capacity < 2 * int(chunk):
-                raise ValueError(f"evaluate_spread: trace_capacity={rec.trace_capacity} is below twice the {int(chunk)} rounds "
-                                 f"played between two drains of the traces")
+        check_rides("evaluate_spread", name, rec, venv, chunk=chunk)
     venv.scalars().zero_()                     # the episode cursors count from 0 again: this pass starts at the top
     for rec in (recorder, decisions):
         if rec is not None:

@@ -25,7 +25,7 @@ template <int W>
 __global__ __launch_bounds__(256) void decision_record_kernel(mel_decision_record g, mel_env_batch e, const float* __restrict__ logits,
                                                               const int32_t* __restrict__ act, const int32_t* __restrict__ row_offsets,
                                                               const uint64_t* __restrict__ live) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = wave_env();
     if (b >= g.n_envs) return;
     const int lane = lane_id();
     const int n = e.n_nodes;
@@ -101,22 +101,10 @@ __global__ __launch_bounds__(256) void decision_record_kernel(mel_decision_recor
     } else if (lane == 0) {
         g.overflow[b] += count;
     }
-    // trace sink: is this env listed?  (n_trace <= MEL_DR_MAX_TRACE: a scalar walk over the launch's own arguments)
-    int t = -1;
-    for (int k = 0; k < g.n_trace; ++k) t = g.trace_env[k] == b ? k : t;
+    const int t = trace_slot(g, b);                                  // trace sink: is this env listed?
     if (t >= 0) {
-        const long long cur = (long long)uniform_u64((uint64_t)g.trace_cursor[t]);
-        const size_t rec = (size_t)t * g.trace_capacity + (size_t)(cur % g.trace_capacity);
-        if (lane < 8) {
-            int m = b;
-            m = lane == 1 ? ep : m;
-            m = lane == 2 ? sc[MEL_S_EPISODE] : m;
-            m = lane == 3 ? mv : m;
-            m = lane == 4 ? count : m;
-            m = lane == 5 ? ns_count(relaying) : m;
-            m = lane >= 6 ? 0 : m;
-            g.trace_meta[rec * 8 + lane] = m;
-        }
+        const TraceRecord tr = trace_open(g, t, lane, b, ep, sc[MEL_S_EPISODE], mv, count, ns_count(relaying));
+        const size_t rec = tr.rec;
         MEL_W_FOR(w) {
             if (lane == w) g.trace_sets[rec * 2 * W + w] = deciding.w[w];
             if (lane == W + w) g.trace_sets[rec * 2 * W + W + w] = relaying.w[w];
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(256) void decision_record_kernel(mel_decision_recor
                 g.trace_q[(rec * n + node) * 2 + 1] = q1[h];
             }
         }
-        if (lane == 0) g.trace_cursor[t] = cur + 1;
+        trace_close(g, t, lane, tr);
     }
 }
 
@@ -137,20 +125,12 @@ __global__ __launch_bounds__(256) void decision_record_read_kernel(mel_decision_
                                                                    long long* __restrict__ counters_out) {
     const size_t per_round = (size_t)g.max_rounds * MEL_DR_FIELDS, per_degree = (size_t)g.n_degrees * MEL_DR_FIELDS;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;            // (row, field): the rounds' rows, then the degrees'
-    if (i < per_round) {
-        double s = 0.0;
-        for (int b = 0; b < g.n_envs; ++b) s += g.by_round[(size_t)b * per_round + i];
-        by_round_out[i] = s;
-    } else if (i < per_round + per_degree) {
-        const size_t j = i - per_round;
-        double s = 0.0;
-        for (int b = 0; b < g.n_envs; ++b) s += g.by_degree[(size_t)b * per_degree + j];
-        by_degree_out[j] = s;
-    }
+    if (i < per_round) by_round_out[i] = fold_rows(g.by_round, g.n_envs, per_round, i);
+    else if (i < per_round + per_degree) by_degree_out[i - per_round] = fold_rows(g.by_degree, g.n_envs, per_degree, i - per_round);
     if (i == 0) {
-        long long over = 0, skip = 0;
-        for (int b = 0; b < g.n_envs; ++b) over += g.overflow[b], skip += g.skipped[b];
-        counters_out[MEL_DRC_OVERFLOW] = over, counters_out[MEL_DRC_SKIPPED] = skip, counters_out[2] = 0, counters_out[3] = 0;
+        counters_out[MEL_DRC_OVERFLOW] = fold_counter(g.overflow, g.n_envs);
+        counters_out[MEL_DRC_SKIPPED] = fold_counter(g.skipped, g.n_envs);
+        counters_out[2] = 0, counters_out[3] = 0;
     }
 }
 
@@ -162,21 +142,7 @@ inline mel_status check_decision_record(const mel_decision_record* g, const char
         g->n_envs < 1 || g->n_nodes < 1 || g->n_nodes > MEL_MAX_NODES)
         return fail(MEL_ERR_INVALID_ARG, "%s: max_rounds=%d outside [1, %d], n_degrees=%d outside [1, %d], n_envs=%d < 1 or n_nodes=%d outside [1, %d]",
                     who, g->max_rounds, MEL_DR_MAX_ROUNDS, g->n_degrees, MEL_DR_MAX_DEGREES, g->n_envs, g->n_nodes, MEL_MAX_NODES);
-    if (g->n_trace < 0 || g->n_trace > MEL_DR_MAX_TRACE)
-        return fail(MEL_ERR_INVALID_ARG, "%s: n_trace=%d outside [0, %d]", who, g->n_trace, MEL_DR_MAX_TRACE);
-    if (g->n_trace > 0) {
-        if (g->trace_capacity < 1) return fail(MEL_ERR_INVALID_ARG, "%s: trace_capacity=%d must be >= 1", who, g->trace_capacity);
-        if (!g->trace_cursor || !g->trace_meta || !g->trace_sets || !g->trace_q)
-            return fail(MEL_ERR_INVALID_ARG, "%s: the trace sink has a null buffer", who);
-        for (int k = 0; k < g->n_trace; ++k) {
-            if (g->trace_env[k] < 0 || g->trace_env[k] >= g->n_envs)
-                return fail(MEL_ERR_INVALID_ARG, "%s: traced env %d is outside [0, %d)", who, g->trace_env[k], g->n_envs);
-            for (int j = 0; j < k; ++j)
-                if (g->trace_env[j] == g->trace_env[k])
-                    return fail(MEL_ERR_INVALID_ARG, "%s: env %d is traced twice", who, g->trace_env[k]);
-        }
-    }
-    return MEL_OK;
+    return check_trace_sink(g, who, g->trace_sets && g->trace_q);
 }
 
 }  // namespace mel
@@ -199,10 +165,10 @@ mel_status mel_decision_record_round(const mel_decision_record* rec, const mel_e
         return mel::fail(MEL_ERR_UNSUPPORTED, "mel_decision_record_round: n_actions=%d, the record is of two actions (relay is action 1)",
                          n_actions);
     mel::clear_stale_error();
-    const dim3 grid((unsigned)((rec->n_envs + 3) / 4));
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (env->n_nodes > 64) MEL_LAUNCH(mel::decision_record_kernel<2>, grid, dim3(256), 0, s, *rec, *env, logits, act, row_offsets, live);
-    else MEL_LAUNCH(mel::decision_record_kernel<1>, grid, dim3(256), 0, s, *rec, *env, logits, act, row_offsets, live);
+    mel::with_env_waves(rec->n_envs, env->n_nodes, [&](auto w, dim3 grid, dim3 block) {
+        MEL_LAUNCH(mel::decision_record_kernel<decltype(w)::value>, grid, block, 0, static_cast<hipStream_t>(stream), *rec, *env, logits,
+                   act, row_offsets, live);
+    });
     return mel::check_launch("mel_decision_record_round");
 }
 

@@ -1494,5 +1494,6 @@ mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n
 }  // extern "C"
 
 #include "train_log.hpp"      // mel_train_log_round / mel_train_log_update: training curves summed per interval on the device
+#include "record_common.hpp"  // the trace ring, the fold over the envs and the launch geometry of the two recorders below
 #include "round_record.hpp"   // mel_round_record_round / mel_round_record_read: per-round curves and traces of an evaluation
 #include "decision_record.hpp"   // mel_decision_record_round / mel_decision_record_read: the policy's decisions per round and degree

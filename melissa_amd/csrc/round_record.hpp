@@ -19,7 +19,7 @@ namespace mel {
 
 template <int W>
 __global__ __launch_bounds__(256) void round_record_kernel(mel_round_record g, mel_env_batch e) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = wave_env();
     if (b >= g.n_envs) return;
     const int lane = lane_id();
     const int n = e.n_nodes;
@@ -115,22 +115,10 @@ __global__ __launch_bounds__(256) void round_record_kernel(mel_round_record g, m
         }
         if (lane < MEL_RR_FIELDS) last[lane] = v;
         last_r = mv, last_full = full;
-        // trace sink: is this env listed?  (n_trace <= MEL_RR_MAX_TRACE: a scalar walk over the launch's own arguments)
-        int t = -1;
-        for (int k = 0; k < g.n_trace; ++k) t = g.trace_env[k] == b ? k : t;
+        const int t = trace_slot(g, b);                              // trace sink: is this env listed?
         if (t >= 0) {
-            const long long cur = (long long)uniform_u64((uint64_t)g.trace_cursor[t]);
-            const size_t rec = (size_t)t * g.trace_capacity + (size_t)(cur % g.trace_capacity);
-            if (lane < 8) {
-                int m = b;
-                m = lane == 1 ? ep : m;
-                m = lane == 2 ? sc[MEL_S_EPISODE] : m;
-                m = lane == 3 ? mv : m;
-                m = lane == 4 ? sc[MEL_S_ORIGIN] : m;
-                m = lane == 5 ? msgs : m;
-                m = lane >= 6 ? 0 : m;
-                g.trace_meta[rec * 8 + lane] = m;
-            }
+            const TraceRecord tr = trace_open(g, t, lane, b, ep, sc[MEL_S_EPISODE], mv, sc[MEL_S_ORIGIN], msgs);
+            const size_t rec = tr.rec;
             const size_t node0 = (size_t)b * n;
             for (int c = lane; c < 2 * n; c += 64) g.trace_pos[rec * 2 * n + c] = e.pos[node0 * 2 + c];
             for (int c = lane; c < n * W; c += 64) g.trace_one_hop[rec * n * W + c] = e.one_hop[node0 * W + c];
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(256) void round_record_kernel(mel_round_record g, m
                 g.trace_agent_msgs[rec * n + c] = e.agent_msgs[node0 + c];
                 g.trace_received[rec * n + c] = e.received[node0 + c];
             }
-            if (lane == 0) g.trace_cursor[t] = cur + 1;
+            trace_close(g, t, lane, tr);
         }
     }
     if (lane == 0) {
@@ -157,14 +145,13 @@ __global__ __launch_bounds__(256) void round_record_read_kernel(mel_round_record
     const size_t per = (size_t)g.max_rounds * MEL_RR_FIELDS;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;            // (round, field)
     if (i < per) {
-        double run = 0.0, end = 0.0;
-        for (int b = 0; b < g.n_envs; ++b) run += g.running[(size_t)b * per + i], end += g.ended[(size_t)b * per + i];
-        running_out[i] = run, ended_out[i] = end;
+        running_out[i] = fold_rows(g.running, g.n_envs, per, i);
+        ended_out[i] = fold_rows(g.ended, g.n_envs, per, i);
     }
     if (i == 0) {
-        long long over = 0, skip = 0, unlogged = 0;
-        for (int b = 0; b < g.n_envs; ++b) over += g.overflow[b], skip += g.skipped[b], unlogged += g.unlogged[b];
-        counters_out[MEL_RRC_OVERFLOW] = over, counters_out[MEL_RRC_SKIPPED] = skip, counters_out[MEL_RRC_UNLOGGED] = unlogged;
+        counters_out[MEL_RRC_OVERFLOW] = fold_counter(g.overflow, g.n_envs);
+        counters_out[MEL_RRC_SKIPPED] = fold_counter(g.skipped, g.n_envs);
+        counters_out[MEL_RRC_UNLOGGED] = fold_counter(g.unlogged, g.n_envs);
     }
 }
 
@@ -175,22 +162,7 @@ inline mel_status check_round_record(const mel_round_record* g, const char* who)
     if (g->max_rounds < 1 || g->max_rounds > MEL_RR_MAX_ROUNDS || g->n_envs < 1 || g->n_nodes < 1 || g->n_nodes > MEL_MAX_NODES)
         return fail(MEL_ERR_INVALID_ARG, "%s: max_rounds=%d outside [1, %d], n_envs=%d < 1 or n_nodes=%d outside [1, %d]", who,
                     g->max_rounds, MEL_RR_MAX_ROUNDS, g->n_envs, g->n_nodes, MEL_MAX_NODES);
-    if (g->n_trace < 0 || g->n_trace > MEL_RR_MAX_TRACE)
-        return fail(MEL_ERR_INVALID_ARG, "%s: n_trace=%d outside [0, %d]", who, g->n_trace, MEL_RR_MAX_TRACE);
-    if (g->n_trace > 0) {
-        if (g->trace_capacity < 1) return fail(MEL_ERR_INVALID_ARG, "%s: trace_capacity=%d must be >= 1", who, g->trace_capacity);
-        if (!g->trace_cursor || !g->trace_meta || !g->trace_pos || !g->trace_one_hop || !g->trace_sets || !g->trace_agent_msgs ||
-            !g->trace_received)
-            return fail(MEL_ERR_INVALID_ARG, "%s: the trace sink has a null buffer", who);
-        for (int k = 0; k < g->n_trace; ++k) {
-            if (g->trace_env[k] < 0 || g->trace_env[k] >= g->n_envs)
-                return fail(MEL_ERR_INVALID_ARG, "%s: traced env %d is outside [0, %d)", who, g->trace_env[k], g->n_envs);
-            for (int j = 0; j < k; ++j)
-                if (g->trace_env[j] == g->trace_env[k])
-                    return fail(MEL_ERR_INVALID_ARG, "%s: env %d is traced twice", who, g->trace_env[k]);
-        }
-    }
-    return MEL_OK;
+    return check_trace_sink(g, who, g->trace_pos && g->trace_one_hop && g->trace_sets && g->trace_agent_msgs && g->trace_received);
 }
 
 }  // namespace mel
@@ -208,9 +180,9 @@ mel_status mel_round_record_round(const mel_round_record* rec, const mel_env_bat
         return mel::fail(MEL_ERR_INVALID_ARG, "mel_round_record_round: the record is for %d envs of %d nodes, the env batch has %d of %d",
                          rec->n_envs, rec->n_nodes, env->n_envs, env->n_nodes);
     mel::clear_stale_error();
-    const dim3 grid((unsigned)((rec->n_envs + 3) / 4));
-    if (env->n_nodes > 64) MEL_LAUNCH(mel::round_record_kernel<2>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), *rec, *env);
-    else MEL_LAUNCH(mel::round_record_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), *rec, *env);
+    mel::with_env_waves(rec->n_envs, env->n_nodes, [&](auto w, dim3 grid, dim3 block) {
+        MEL_LAUNCH(mel::round_record_kernel<decltype(w)::value>, grid, block, 0, static_cast<hipStream_t>(stream), *rec, *env);
+    });
     return mel::check_launch("mel_round_record_round");
 }
 

@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .record_common import TraceRecorder, check_out_args, group_by_ordinal, save_traces  # noqa: F401  (save_traces: this module's too)
 
 FIELDS = ("count", "has_message", "interested_with_message", "interested", "messages", "active_agents",
           "coverage_interested_fraction", "newly_covered")
@@ -30,12 +31,8 @@ QUANTILES = (0.5, 0.9, 1.0)
 
 def check_record_args(spread: bool, curves_out=None, trace_out=None, render_out=None, trace_envs: int = 1) -> None:
     """ValueError for recorder arguments that mean nothing (no torch, nothing built)."""
-    wanted = [n for n, v in (("curves_out", curves_out), ("trace_out", trace_out), ("render_out", render_out)) if v is not None]
-    if wanted and not spread:
-        raise ValueError(f"{', '.join(wanted)}: the per-round recorder runs with the spread evaluation (spread=True / --spread; "
-                         f"with one env that is the reference's own walk down the test list)")
-    if (trace_out is not None or render_out is not None) and not 1 <= int(trace_envs) <= _lib.RR_MAX_TRACE:
-        raise ValueError(f"trace_envs={trace_envs} outside [1, {_lib.RR_MAX_TRACE}]")
+    check_out_args("per-round recorder", spread, dict(curves_out=curves_out, trace_out=trace_out, render_out=render_out),
+                   trace_out is not None or render_out is not None, trace_envs)
 
 
 def summarise(running, ended, n_nodes: "int | None" = None, quantiles=QUANTILES) -> dict:
@@ -73,59 +70,30 @@ def group_episodes(records: list) -> list:
     """Trace records of ONE env in play order -> one dict per episode ordinal: ``env``, ``ordinal``, ``pool_episode``, ``origin``,
     ``rounds`` [K], ``world_msgs`` [K], ``pos`` [K, N, 2], ``one_hop`` uint64 [K, N, W], ``sets`` uint64 [K, 6, W]
     (``_lib.RR_TRACE_SETS``), ``agent_msgs`` / ``received`` int32 [K, N]."""
-    episodes, run = [], []
-
-    def close():
-        if run:
-            m = np.stack([r["meta"] for r in run])
-            episodes.append(dict(env=int(m[0, 0]), ordinal=int(m[0, 1]), pool_episode=int(m[0, 2]), origin=int(m[0, 4]),
-                                 rounds=m[:, 3].copy(), world_msgs=m[:, 5].copy(),
-                                 **{k: np.stack([r[k] for r in run]) for k in ("pos", "one_hop", "sets", "agent_msgs", "received")}))
-            run.clear()
-
-    for rec in records:
-        if run and int(rec["meta"][1]) != int(run[0]["meta"][1]):
-            close()
-        run.append(rec)
-    close()
-    return episodes
+    return group_by_ordinal(records, scalars=dict(origin=4), series=dict(world_msgs=5),
+                            arrays=("pos", "one_hop", "sets", "agent_msgs", "received"))
 
 
-def save_traces(path, traces: dict) -> None:
-    """``{env: [episode, ...]}`` (:meth:`RoundRecorder.drain_traces`) as one ``.npz``: key ``e<env>_o<ordinal>_<array>``."""
-    flat = {}
-    for env, episodes in traces.items():
-        for ep in episodes:
-            for k, v in ep.items():
-                flat[f"e{int(env)}_o{ep['ordinal']}_{k}"] = np.asarray(v)
-    with open(path, "wb") as f:
-        np.savez(f, **flat)
-
-
-class RoundRecorder:
+class RoundRecorder(TraceRecorder):
     """Owner of one ``mel_round_record`` and its device buffers for the envs of ``venv``.  ``max_rounds``: round indices kept
     (default: the env's ``max_moves + 1``); ``trace_envs``: up to 16 env ids whose per-node state is kept after every round, in
     a ring of ``trace_capacity`` records each; ``quota``: per env, how many of its episodes count (None: all).  Give it to
     :class:`melissa_amd.collect.RoundLoop` (``recorder=``) BEFORE the loop captures its rounds: captured launches hold the pointers
     and the sizes."""
 
+    group = staticmethod(group_episodes)
+
+    @staticmethod
+    def trace_spec(n: int, W: int) -> dict:
+        return dict(pos=((n, 2), "float64"), one_hop=((n, W), "int64"), sets=((6, W), "int64"), agent_msgs=((n,), "int32"),
+                    received=((n,), "int32"))
+
     def __init__(self, venv, max_rounds: "int | None" = None, trace_envs=(), trace_capacity: int = 64, quota=None, device=None,
                  log_capacity: int = 65536):
         import torch
         if int(venv.env.log_capacity) < 1:
             venv.enable_episode_log(int(log_capacity))       # (a Collector built afterwards replaces it with its own)
-        B, n = int(venv.env_num), int(venv.n)
-        R = int(venv.max_moves) + 1 if max_rounds is None else int(max_rounds)
-        trace_envs = [int(t) for t in trace_envs]
-        if not 1 <= R <= _lib.RR_MAX_ROUNDS:
-            raise ValueError(f"RoundRecorder: max_rounds={R} outside [1, {_lib.RR_MAX_ROUNDS}]")
-        if len(trace_envs) > _lib.RR_MAX_TRACE or len(set(trace_envs)) != len(trace_envs) or any(not 0 <= t < B for t in trace_envs):
-            raise ValueError(f"RoundRecorder: trace_envs={trace_envs}: at most {_lib.RR_MAX_TRACE} distinct envs of [0, {B})")
-        if trace_envs and int(trace_capacity) < 1:
-            raise ValueError(f"RoundRecorder: trace_capacity={trace_capacity} must be >= 1")
-        self.venv, self.max_rounds, self.trace_envs, self.trace_capacity = venv, R, trace_envs, int(trace_capacity)
-        self.device = dev = torch.device(device) if device is not None else venv.device
-        T, cap, W = len(trace_envs), int(trace_capacity), _lib.set_words(n)
+        B, n, R, dev = self._setup(venv, max_rounds, trace_envs, trace_capacity, device)
         f64, i32, i64 = torch.float64, torch.int32, torch.int64
         self.running = torch.zeros(B, R, _lib.RR_FIELDS, dtype=f64, device=dev)
         self.ended = torch.zeros(B, R, _lib.RR_FIELDS, dtype=f64, device=dev)
@@ -134,29 +102,12 @@ class RoundRecorder:
         self.overflow = torch.zeros(B, dtype=i64, device=dev)
         self.skipped = torch.zeros(B, dtype=i64, device=dev)
         self.unlogged = torch.zeros(B, dtype=i64, device=dev)
-        self.quota = torch.zeros(B, dtype=i32, device=dev)
         self._out = torch.zeros(2, R, _lib.RR_FIELDS, dtype=f64, device=dev)
         self._counters = torch.zeros(4, dtype=i64, device=dev)
         self.c = c = _lib.MelRoundRecord()
         c.running, c.ended, c.seen, c.last = self.running.data_ptr(), self.ended.data_ptr(), self.carry.data_ptr(), self.last.data_ptr()
         c.overflow, c.skipped, c.unlogged = self.overflow.data_ptr(), self.skipped.data_ptr(), self.unlogged.data_ptr()
-        c.n_envs, c.n_nodes, c.max_rounds, c.n_trace, c.trace_capacity = B, n, R, T, cap if T else 0
-        if T:
-            self.trace_cursor = torch.zeros(T, dtype=i64, device=dev)
-            self.trace_meta = torch.zeros(T, cap, 8, dtype=i32, device=dev)
-            self.trace_pos = torch.zeros(T, cap, n, 2, dtype=f64, device=dev)
-            self.trace_one_hop = torch.zeros(T, cap, n, W, dtype=i64, device=dev)
-            self.trace_sets = torch.zeros(T, cap, 6, W, dtype=i64, device=dev)
-            self.trace_agent_msgs = torch.zeros(T, cap, n, dtype=i32, device=dev)
-            self.trace_received = torch.zeros(T, cap, n, dtype=i32, device=dev)
-            for name in ("trace_cursor", "trace_meta", "trace_pos", "trace_one_hop", "trace_sets", "trace_agent_msgs", "trace_received"):
-                setattr(c, name, getattr(self, name).data_ptr())
-            for k, t in enumerate(trace_envs):
-                c.trace_env[k] = t
-        self._drained = [0] * T
-        self.records = {t: [] for t in trace_envs}           # every record drained since reset(), per traced env
-        self.lost = 0                                        # records overwritten before they were read, since reset()
-        self.set_quota(quota)
+        self._bind_ring(quota)
 
     # ------------------------------------------------------------------ launch (capturable: no host read, no allocation)
     def launch(self) -> None:
@@ -165,29 +116,12 @@ class RoundRecorder:
                    "mel_round_record_round")
 
     # ------------------------------------------------------------------ host side
-    def set_quota(self, quota) -> None:
-        """Per env, how many of its episodes count (samples of later ones are not taken); None: no limit.  The VALUES live on
-        the device, but whether there is a quota at all is fixed into a captured launch: set it before the loop is built."""
-        import torch
-        if quota is None:
-            self.c.quota = None
-            return
-        q = torch.as_tensor(np.asarray(quota, dtype=np.int32))
-        if q.shape != (self.venv.env_num,):
-            raise ValueError(f"RoundRecorder: quota has shape {tuple(q.shape)}, one value per env ({self.venv.env_num}) is needed")
-        self.quota.copy_(q)
-        self.c.quota = self.quota.data_ptr()
-
     def reset(self) -> None:
         """Zero the accumulators and the counters, forget the carry (``seen`` = -1) and every trace record."""
         for t in (self.running, self.ended, self.last, self.overflow, self.skipped, self.unlogged):
             t.zero_()
         self.carry.fill_(-1)
-        if self.trace_envs:
-            self.trace_cursor.zero_()
-        self._drained = [0] * len(self.trace_envs)
-        self.records = {t: [] for t in self.trace_envs}
-        self.lost = 0
+        self._reset_ring()
 
     @property
     def seen(self):
@@ -206,24 +140,3 @@ class RoundRecorder:
         out, counters = self._out.cpu().numpy(), self._counters.cpu().tolist()
         return out[0], out[1], dict(overflow=int(counters[_lib.RRC_OVERFLOW]), skipped=int(counters[_lib.RRC_SKIPPED]),
                                     unlogged=int(counters[_lib.RRC_UNLOGGED]))
-
-    def drain_traces(self):
-        """Read the records written since the last drain (synchronises) -> (``{env: [episode, ...]}`` of EVERY record drained
-        since :meth:`reset`, in play order and grouped by episode ordinal (:func:`group_episodes`), records overwritten before
-        they were read since :meth:`reset`)."""
-        import torch
-        if self.trace_envs:
-            torch.cuda.synchronize(self.device)
-            cursors = self.trace_cursor.cpu().tolist()
-            host = {k: getattr(self, "trace_" + k).cpu().numpy() for k in ("meta", "pos", "one_hop", "sets", "agent_msgs", "received")}
-            host["one_hop"], host["sets"] = host["one_hop"].view(np.uint64), host["sets"].view(np.uint64)
-            cap = self.trace_capacity
-            for t, env in enumerate(self.trace_envs):
-                cur, first = int(cursors[t]), self._drained[t]
-                if cur - first > cap:
-                    self.lost += cur - cap - first
-                    first = cur - cap
-                for j in range(first, cur):
-                    self.records[env].append({k: v[t, j % cap].copy() for k, v in host.items()})
-                self._drained[t] = cur
-        return {env: group_episodes(recs) for env, recs in self.records.items()}, self.lost

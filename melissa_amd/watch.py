@@ -160,6 +160,16 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     return {k: out[k] for k in keys}
 
 
+def as_json(v):
+    """A summary for ``json.dump``: arrays as lists, NaN (a ratio over nothing) as null, dict keys (the ``delay`` quantiles) as strings."""
+    if isinstance(v, dict):
+        return {str(k): as_json(x) for k, x in v.items()}
+    v = v.tolist() if hasattr(v, "tolist") else v
+    if isinstance(v, list):
+        return [as_json(x) for x in v]
+    return None if isinstance(v, float) and v != v else v
+
+
 def write_record(recorder, n_nodes: int, curves_out=None, trace_out=None, render_out=None) -> None:
     """What the recorder holds after an evaluation, into the files the caller asked for."""
     from .render import write_svg_frames
@@ -167,9 +177,7 @@ def write_record(recorder, n_nodes: int, curves_out=None, trace_out=None, render
     running, ended, counters = recorder.curves()
     traces, lost = recorder.drain_traces()
     if curves_out is not None:
-        summary = summarise(running, ended, n_nodes=n_nodes)
-        doc = {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in summary.items() if k != "delay"}
-        doc["delay"] = {str(q): r for q, r in summary["delay"].items()}
+        doc = as_json(summarise(running, ended, n_nodes=n_nodes))
         doc.update(running_sums=running.tolist(), ended_sums=ended.tolist(), counters=dict(counters, lost_trace_records=int(lost)))
         with open(curves_out, "w") as f:
             json.dump(doc, f)
@@ -187,14 +195,6 @@ def write_decisions(decisions, decisions_out=None, decision_trace_out=None) -> N
     by_round, by_degree, counters = decisions.tables()
     traces, lost = decisions.drain_traces()
     if decisions_out is not None:
-        def as_json(v):                                  # arrays as lists; NaN (a ratio over no decision) as null
-            if isinstance(v, dict):
-                return {k: as_json(x) for k, x in v.items()}
-            v = v.tolist() if hasattr(v, "tolist") else v
-            if isinstance(v, list):
-                return [as_json(x) for x in v]
-            return None if isinstance(v, float) and v != v else v
-
         doc = as_json(summarise_decisions(by_round, by_degree))
         doc.update(by_round_sums=by_round.tolist(), by_degree_sums=by_degree.tolist(),
                    counters=dict(counters, lost_trace_records=int(lost)))

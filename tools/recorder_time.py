@@ -1,13 +1,16 @@
-"""Cost of the per-round recorder (melissa_amd/round_record.py): one more launch behind every env round.
+"""Cost of a device recorder - the per-round recorder (melissa_amd/round_record.py: one more launch behind every env round) or the
+decision recorder (melissa_amd/decision_record.py: one more launch between every round's forward and env launch).
 
-The per-round time of the graph-replayed L-DGN round loop, three ways on this tree - recorder off, on with curves only, on with
-four traced envs - and, with ``--parent-tree DIR`` (a checkout of the parent commit with its library built), the same loop on the
-parent's code.  Every figure comes from a loop built anew (same seeds, same trajectory, the same rounds timed), a block is timed
-on the host between two synchronisations, and the variants ALTERNATE: block k of every variant runs before block k + 1 of any,
-each tree in a fresh child process.  Reported per variant: the median of the blocks with their minimum and maximum in
-microseconds per round, the spread (largest max - min of a variant), and the differences of the medians.
+The per-round time of the graph-replayed L-DGN round loop, three ways - recorder off, on without traces, on with four traced
+envs - on this tree and, with ``--parent-tree DIR`` (a checkout of the parent commit with its library built), on the parent's:
+every variant a tree offers is run on it and labelled ``<tree>_<variant>``.  Every figure comes from a loop built anew (same
+seeds, same trajectory, the same rounds timed), a block is timed on the host between two synchronisations, and the variants
+ALTERNATE: block k of every variant runs before block k + 1 of any, each tree in a fresh child process.  Reported per variant:
+the median of the blocks with their minimum and maximum in microseconds per round, the spread (largest max - min of a variant),
+the recorder's cost on each tree and, per variant, this tree's median minus the parent's.
 
-    python tools/round_record_time.py [--envs 1024] [--nodes 50] [--rounds 400] [--blocks 3] [--parent-tree DIR] [--out FILE]
+    python tools/recorder_time.py --recorder round|decisions [--envs 1024] [--nodes 50] [--rounds 400] [--blocks 3]
+                                  [--parent-tree DIR] [--out FILE]
 """
 import argparse
 import gc
@@ -19,30 +22,34 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-VARIANTS = ("off", "curves", "trace4")
+VARIANTS = ("off", "on", "trace4")
+# --recorder -> (module, class, the RoundLoop argument)
+RECORDERS = {"round": ("round_record", "RoundRecorder", "recorder"), "decisions": ("decision_record", "DecisionRecorder", "decisions")}
 
 
 def child(a):
     """One block of every variant the tree offers, on the tree ``a.tree``; prints {variant: us per round, ...}."""
     sys.path.insert(0, os.path.abspath(a.tree))
+    import importlib
     import torch
     from melissa_amd.collect import RoundLoop
     from melissa_amd.env import HipGraphVectorEnv, synthetic_graph_pool
     from melissa_amd.policy import DQNPolicy
     from melissa_amd.train import build_network
+    module, cls, arg = RECORDERS[a.recorder]
     try:
-        from melissa_amd.round_record import RoundRecorder
+        Recorder = getattr(importlib.import_module("melissa_amd." + module), cls)
     except ImportError:
-        RoundRecorder = None                      # the parent commit: the loop as it was
+        Recorder = None                           # a tree from before the recorder: the loop as it was
     out = {}
-    for variant in (VARIANTS if RoundRecorder is not None else ("parent",)):
+    for variant in (VARIANTS if Recorder is not None else VARIANTS[:1]):
         torch.manual_seed(0)
         net = build_network("l_dgn", a.nodes, torch.device("cuda"))
         venv = HipGraphVectorEnv(a.envs, a.nodes, graph_pool=synthetic_graph_pool(a.nodes, 16, first_seed=0), dynamic_graph=True,
                                  device="cuda", max_moves=48, construct_like_reference=False)
         kw = {}
-        if variant in ("curves", "trace4"):
-            kw["recorder"] = RoundRecorder(venv, trace_envs=range(4) if variant == "trace4" else (), trace_capacity=64)
+        if variant != "off":
+            kw[arg] = Recorder(venv, trace_envs=range(4) if variant == "trace4" else (), trace_capacity=64)
         loop = RoundLoop(venv, DQNPolicy(net), seed=1, eps=0.05, use_graph=True, graph_rounds=a.graph_rounds, **kw)
         with torch.no_grad():
             loop.run(2 + 8 * a.graph_rounds)       # warm-up, both captures, past the first episodes
@@ -53,16 +60,19 @@ def child(a):
             out[variant] = (time.perf_counter() - t0) / a.rounds * 1e6
         c = loop.counters()
         out[variant + "_decisions"], out[variant + "_errors"] = c["decisions"], c["errors"]
-        if "recorder" in kw:
-            out[variant + "_counters"] = kw["recorder"].curves()[2]
+        if a.recorder == "round" and kw:
+            out[variant + "_counters"] = kw[arg].curves()[2]
+        elif kw:
+            by_round, by_degree, counters = kw[arg].tables()
+            out[variant + "_counters"] = dict(counters, booked=float(by_degree[:, 0].sum()))
         del loop, venv, net, kw
         gc.collect()
     print("RESULT " + json.dumps(out))
 
 
 def run_child(a, tree):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--envs", str(a.envs), "--nodes", str(a.nodes),
-           "--rounds", str(a.rounds), "--graph-rounds", str(a.graph_rounds)]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--recorder", a.recorder, "--envs", str(a.envs),
+           "--nodes", str(a.nodes), "--rounds", str(a.rounds), "--graph-rounds", str(a.graph_rounds)]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=a.child_timeout)
     lines = [l for l in res.stdout.splitlines() if l.startswith("RESULT ")]
     if res.returncode != 0 or not lines:
@@ -77,6 +87,7 @@ def summary(blocks):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--recorder", choices=sorted(RECORDERS), required=True)
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--nodes", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=400, help="rounds per block")
@@ -90,23 +101,24 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
+    trees = ([("parent", a.parent_tree)] if a.parent_tree else []) + [("this", os.path.dirname(HERE))]
     blocks, extra = {}, {}
     for _ in range(a.blocks):
-        for tree in ([a.parent_tree] if a.parent_tree else []) + [os.path.dirname(HERE)]:
+        for label, tree in trees:
             for k, v in run_child(a, tree).items():
-                if k in VARIANTS or k == "parent":
-                    blocks.setdefault(k, []).append(v)
-                else:
-                    extra.setdefault(k, []).append(v)
-    out = dict(envs=a.envs, nodes=a.nodes, rounds_per_block=a.rounds, graph_rounds=a.graph_rounds, blocks=a.blocks)
+                (blocks if k in VARIANTS else extra).setdefault(f"{label}_{k}", []).append(v)
+    out = dict(recorder=a.recorder, envs=a.envs, nodes=a.nodes, rounds_per_block=a.rounds, graph_rounds=a.graph_rounds, blocks=a.blocks)
     for name, values in blocks.items():
         out[f"round_us_{name}"] = summary(values)
     out["spread_us"] = round(max(s["max"] - s["min"] for k, s in out.items() if k.startswith("round_us_")), 2)
     med = lambda name: out[f"round_us_{name}"]["median"]
-    if "parent" in blocks:
-        out["off_minus_parent_us"] = round(med("off") - med("parent"), 2)
-        out["off_equals_parent_within_spread"] = abs(out["off_minus_parent_us"]) <= out["spread_us"]
-    out["curves_cost_us"], out["trace4_cost_us"] = round(med("curves") - med("off"), 2), round(med("trace4") - med("off"), 2)
+    for label, _ in trees:
+        for variant in VARIANTS[1:]:
+            if f"{label}_{variant}" in blocks:
+                out[f"{label}_{variant}_cost_us"] = round(med(f"{label}_{variant}") - med(f"{label}_off"), 2)
+    if a.parent_tree:
+        out["this_minus_parent_us"] = {v: round(med(f"this_{v}") - med(f"parent_{v}"), 2) for v in VARIANTS if f"parent_{v}" in blocks}
+        out["equals_parent_within_spread"] = all(abs(d) <= out["spread_us"] for d in out["this_minus_parent_us"].values())
     decisions = {k[:-len("_decisions")]: v for k, v in extra.items() if k.endswith("_decisions")}
     out["same_trajectory"] = len({tuple(v) for v in decisions.values()}) == 1
     out["errors"] = max(max(v) for k, v in extra.items() if k.endswith("_errors"))
