@@ -425,6 +425,28 @@ mel_status mel_hldgn_forward_envs(const mel_weights* w, int32_t aggregator, cons
 mel_status mel_forward_tap(const mel_weights* w, int32_t kind, int64_t bs, int32_t n_nodes, int64_t rows_cap,
                            const void* workspace, void* out, void* stream);
 
+/* mel_forward_attention: the attention coefficients conv2 of the INFERENCE path aggregated with in the last
+ * mel_ldgn_forward_agents / mel_dgnr_forward_agents call with the same (w, bs, n_nodes, rows_cap) and this workspace.  The
+ * forward's conv2 attention keeps only the aggregate x_3; x_l2, x_r2, the conv2 target descriptors and the device-side row count
+ * stay in the workspace until the next forward (nothing behind the conv2 attention writes them, in row-list and in table mode
+ * alike), and ONE launch of its own - a wavefront per agent row - reads them again:
+ *   alpha    device float  [rows_cap][MEL_ATT_MAX_SOURCES][heads]; slot k = the coefficient of the row's k-th source in ASCENDING
+ *            node id, per head; slots from the row's source count on are written 0.  MEL_ATT_MAX_SOURCES = the neighbour cap of
+ *            the radius rule (33) + the GATv2 self-loop.
+ *   sources  device uint64 [rows_cap][MEL_SET_WORDS(n_nodes)]: the row's conv2 source set - GATv2: the closed neighbourhood of
+ *            the agent; TransformerConv: the open one, so an isolated agent has an all-zero set and an all-zero alpha row.
+ * Only the rows below the device-side agent-row count (row_offsets[bs] of the forward) are written, nothing else is touched.
+ * Arithmetic, per head: the forward's sources, its score (GATv2: att . leaky_relu(x_l[j] + x_r[i], 0.2); TransformerConv:
+ * q[i] . k[j] / sqrt(C)), alpha_k = e^(s_k - max s) * (1 / (sum_j e^(s_j - max s) + 1e-16)) with the forward's exp2-based exp and
+ * its reciprocal, the sum taken in ascending source order (the forward streams the same terms through an online softmax, two
+ * sources per step: the two agree within fp32 rounding, not bit for bit).
+ * No host read, no allocation: it replays from a HIP graph.  MEL_ERR_UNSUPPORTED: HL-DGN weights (no conv2, no agent rows),
+ * MEL_PREC_BF16 (bf16 rows), a head shape the attention kernels do not run.  MEL_ERR_INVALID_ARG: a null argument, bs / n_nodes
+ * out of range, rows_cap outside [1, bs * n_nodes]. */
+#define MEL_ATT_MAX_SOURCES 34
+mel_status mel_forward_attention(const mel_weights* w, int64_t bs, int32_t n_nodes, int64_t rows_cap,
+                                 const void* workspace, float* alpha, uint64_t* sources, void* stream);
+
 /* [3P] DQNPolicy.forward + exploration_noise:
  *   q = logits + (1 - mask) * (min(logits) - max(logits) - 1)   (batch-wide min / max)
  *   act = argmax(q);  if rand_u[b] < eps: act = argmax(rand_q[b, :] + mask)
@@ -1204,6 +1226,74 @@ mel_status mel_decision_record_round(const mel_decision_record* rec, const mel_e
 mel_status mel_decision_record_read(const mel_decision_record* rec, double* by_round_out, double* by_degree_out,
                                     int64_t* counters_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Whom the deciding agents attend to, per round, recorded ON THE DEVICE: does a deciding node listen to neighbours that already
+ * hold the message or to those still waiting for it, and how does that change with the round and with the node's degree.  Like
+ * the decisions, the data exists between two launches only: after the forward, mel_forward_attention (above) turns what the
+ * forward left in its workspace into alpha / sources; mel_env_round then overwrites the state the decision was taken in.  So
+ * mel_attention_record_round sits where mel_decision_record_round sits, behind mel_forward_attention, and reads alpha, sources
+ * and the env's sets as they stand at the launch.  It touches nothing the round loop reads.
+ * All pointers of mel_attention_record are caller-owned DEVICE memory (B = n_envs, R = max_rounds, D = n_degrees, H = n_heads,
+ * N = n_nodes, W = MEL_SET_WORDS(N)); every table is per env, double, written without atomics (an env owns its rows):
+ *   by_round   double [B][R][MEL_AR_FIELDS]  per decision env b took with MEL_S_NUM_MOVES == r: the HEAD MEAN of each field  (start: 0)
+ *   by_degree  double [B][D][MEL_AR_FIELDS]  the same head mean by the deciding node's degree, min(degree, D - 1)             (start: 0)
+ *   by_head    double [B][H][MEL_AR_FIELDS]  the per-head values                                                              (start: 0)
+ *   overflow, skipped, quota: mel_decision_record's, rule for rule.
+ * mel_attention_record_round(rec, env, alpha, sources, row_offsets, live, heads, stream): alpha float [rows][MEL_ATT_MAX_SOURCES]
+ *   [heads] and sources uint64 [rows][W] as mel_forward_attention writes them (members >= N of a source set are ignored),
+ *   row_offsets int32 [B + 1] and live uint64 [B][W] the round's; heads must equal rec->n_heads.
+ * Per env (one wavefront, 4 envs per 256-lane workgroup): the error skip, the quota, the round index MEL_S_NUM_MOVES, the degree
+ * (column 2 of the node's obs_matrix row, clamped to [0, D - 1]), the overflow rule and the walk in ASCENDING node id are
+ * mel_decision_record's.  A decision is a member of live[b] that is not in MEL_SET_SCRIPTED, at row row_offsets[b] + its rank in
+ * live[b].  Per decision of node i and per head h, with a_k = (double)alpha[row][k][h] of the row's k-th source j_k in ascending
+ * node id (k < min(|sources|, MEL_ATT_MAX_SOURCES) = c), every sum starting at 0.0 and taken in that order:
+ *     0 decisions: 1
+ *     1 self: a_k of j_k == i (0 where i is no source of its own: TransformerConv)
+ *     2 informed: sum of a_k over j_k != i in MEL_SET_HAS_MESSAGE          3 that class's size / c
+ *     4 waiting:  sum of a_k over j_k != i in MEL_SET_INTERESTED & ~MEL_SET_HAS_MESSAGE     5 that class's size / c
+ *     6 sum of a_k * a_k (its reciprocal is the effective number of neighbours)             7 max a_k (0 upwards)
+ *   A decision without sources (c == 0) books field 0 only.  The head mean of a field is the sum over the heads in ascending
+ *   order divided by (double)heads.  Additions, multiplications, divisions and comparisons of IEEE doubles in a fixed order,
+ *   no transcendental function: a NumPy restatement gives the tables bit for bit.
+ *   - r >= R: the decision's by_round row is dropped and overflow[b] += 1; by_degree and by_head are still booked;
+ *   - trace sink: the shared one (mel_round_record's: trace_env[], rings, cursor, header, argument errors).  A launch that booked
+ *     at least one decision for a listed env writes the record:
+ *       trace_meta    int32  [T][cap][8]     env, episode ordinal, MEL_S_EPISODE, num_moves, decisions, decisions without sources, 0, 0
+ *       trace_sets    uint64 [T][cap][W]     the deciding set
+ *       trace_fields  double [T][cap][N][MEL_AR_FIELDS]  the node's head-mean fields; 0 for nodes that did not decide
+ *     Records join the other two recorders' records on (env, episode ordinal, num_moves).
+ * mel_attention_record_read: by_round_out [R][8], by_degree_out [D][8], by_head_out [H][8] device doubles = the envs' rows added
+ *   in ascending env order by one thread per element; counters_out device int64 [4] = MEL_DRC_* (overflow, skipped, 0, 0).
+ * Neither reads on the host nor allocates: both replay from a HIP graph.  MEL_ERR_INVALID_ARG: mel_decision_record's cases, a
+ * null alpha / sources / row_offsets / live / by_head, n_heads outside [1, MEL_AR_MAX_HEADS], heads != rec->n_heads. */
+#define MEL_AR_FIELDS       8
+#define MEL_AR_MAX_HEADS   16
+typedef struct mel_attention_record {
+    double*        by_round;
+    double*        by_degree;
+    double*        by_head;
+    int64_t*       overflow;
+    int64_t*       skipped;
+    const int32_t* quota;
+    int64_t*       trace_cursor;
+    int32_t*       trace_meta;
+    uint64_t*      trace_sets;
+    double*        trace_fields;
+    int32_t        n_envs;
+    int32_t        n_nodes;
+    int32_t        max_rounds;
+    int32_t        n_degrees;
+    int32_t        n_heads;
+    int32_t        n_trace;
+    int32_t        trace_capacity;
+    int32_t        trace_env[MEL_DR_MAX_TRACE];
+} mel_attention_record;
+mel_status mel_attention_record_round(const mel_attention_record* rec, const mel_env_batch* env, const float* alpha,
+                                      const uint64_t* sources, const int32_t* row_offsets, const uint64_t* live, int32_t heads,
+                                      void* stream);
+mel_status mel_attention_record_read(const mel_attention_record* rec, double* by_round_out, double* by_degree_out,
+                                     double* by_head_out, int64_t* counters_out, void* stream);
+
 /* last() only (mutates is_new_round exactly like GraphEnv.observe, graph.py:205-211). */
 mel_status mel_env_observe(mel_env_batch* env, const int32_t* env_ids, int64_t n,
                            const mel_env_obs* out, void* stream);
@@ -1241,7 +1331,7 @@ const char* mel_last_error(void);
 /* sizeof() of the structs of this header as the library was compiled, for binding authors to check their mirrors
  * against: which = 0 mel_linear, 1 mel_gatv2, 2 mel_mlp, 3 mel_weights, 4 mel_select, 5 mel_env_batch,
  * 6 mel_episode_pool, 7 mel_env_obs, 8 mel_round_replay, 9 mel_graph_pool, 10 mel_episode_stream, 11 mel_replay_batch, 12 mel_adam_tensors,
- * 13 mel_replay_priority, 14 mel_train_log, 15 mel_round_record, 16 mel_decision_record;
+ * 13 mel_replay_priority, 14 mel_train_log, 15 mel_round_record, 16 mel_decision_record, 17 mel_attention_record;
  * 0 for anything else. */
 size_t mel_abi_sizeof(int32_t which);
 const char* mel_version(void);

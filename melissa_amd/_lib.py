@@ -45,7 +45,8 @@ EXPORTS = ("mel_wait_counter", "mel_feature_tables_bytes", "mel_prepare_feature_
            "mel_prof_read", "mel_last_error", "mel_version", "mel_mpr_sets", "mel_exploration_schedule", "mel_td_target", "mel_td_loss",
            "mel_env_step_stats", "mel_graph_pool_workspace_bytes", "mel_graph_pool_generate", "mel_train_log_scratch_bytes",
            "mel_train_log_round", "mel_train_log_update", "mel_round_record_round", "mel_round_record_read",
-           "mel_decision_record_round", "mel_decision_record_read")
+           "mel_decision_record_round", "mel_decision_record_read", "mel_forward_attention", "mel_attention_record_round",
+           "mel_attention_record_read")
 PREC_F32, PREC_BF16, PREC_F32_SPLIT, PREC_F32_AUTO = 0, 1, 2, 3
 FWD_PLAN_READY = 1          # mel_weights.flags: the plan masks of this call were written by mel_env_round
 FWD_INTEGER_FEATURES = 2    # mel_weights.flags: node features are the env's integers -> node-feature table (melissa_hip.h)
@@ -156,6 +157,20 @@ class MelDecisionRecord(C.Structure):
                 ("trace_q", C.c_void_p), ("n_envs", C.c_int32), ("n_nodes", C.c_int32), ("max_rounds", C.c_int32),
                 ("n_degrees", C.c_int32), ("n_trace", C.c_int32), ("trace_capacity", C.c_int32),
                 ("trace_env", C.c_int32 * DR_MAX_TRACE)]
+
+
+# mel_forward_attention / mel_attention_record: the slots of a row (MEL_ATT_MAX_SOURCES), the row layout (MEL_AR_*) and the struct
+ATT_MAX_SOURCES = 34
+AR_FIELDS, AR_MAX_HEADS = 8, 16
+(AR_DECISIONS, AR_SELF, AR_INFORMED, AR_INFORMED_SHARE, AR_WAITING, AR_WAITING_SHARE, AR_SQUARES, AR_MAX) = range(8)
+
+
+class MelAttentionRecord(C.Structure):
+    _fields_ = [("by_round", C.c_void_p), ("by_degree", C.c_void_p), ("by_head", C.c_void_p), ("overflow", C.c_void_p),
+                ("skipped", C.c_void_p), ("quota", C.c_void_p), ("trace_cursor", C.c_void_p), ("trace_meta", C.c_void_p),
+                ("trace_sets", C.c_void_p), ("trace_fields", C.c_void_p), ("n_envs", C.c_int32), ("n_nodes", C.c_int32),
+                ("max_rounds", C.c_int32), ("n_degrees", C.c_int32), ("n_heads", C.c_int32), ("n_trace", C.c_int32),
+                ("trace_capacity", C.c_int32), ("trace_env", C.c_int32 * DR_MAX_TRACE)]
 
 
 class MelEnvBatch(C.Structure):
@@ -337,6 +352,12 @@ def load(build_if_missing: bool = True):
     lib.mel_decision_record_round.argtypes = [C.POINTER(MelDecisionRecord), E, vp, vp, vp, vp, i32, vp]
     lib.mel_decision_record_read.restype = i32
     lib.mel_decision_record_read.argtypes = [C.POINTER(MelDecisionRecord), vp, vp, vp, vp]
+    lib.mel_forward_attention.restype = i32
+    lib.mel_forward_attention.argtypes = [W, i64, i32, i64, vp, vp, vp, vp]
+    lib.mel_attention_record_round.restype = i32
+    lib.mel_attention_record_round.argtypes = [C.POINTER(MelAttentionRecord), E, vp, vp, vp, vp, i32, vp]
+    lib.mel_attention_record_read.restype = i32
+    lib.mel_attention_record_read.argtypes = [C.POINTER(MelAttentionRecord), vp, vp, vp, vp, vp]
     lib.mel_mpr_sets.restype = i32
     lib.mel_mpr_sets.argtypes = [vp, i32, i32, vp, vp]
     lib.mel_feature_tables_bytes.restype = sz

@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmelissa_hip.so")
-SOURCES = ["fwd.hip", "env.hip", "grad.hip"]
-HEADERS = ["common.hpp", "kprof.hpp", "gemm_f32.hpp", "gemm_walk.hpp", "gemm_bf16.hpp", "gemm_split.hpp", "gemm_ring.hpp", "gemm_table.hpp", "gemm_launch.hpp", "plan.hpp", "plan_masks.hpp", "attention.hpp", "heads.hpp", "episode_stream.hpp", "graph_pool.hpp", "replay_prio.hpp", "td.hpp", "train_log.hpp", "record_common.hpp", "round_record.hpp", "decision_record.hpp",os.path.join("..", "..", "include", "melissa_hip.h")]
+SOURCES = ["fwd.hip", "env.hip", "grad.hip", "attention_record.hip"]
+HEADERS = ["common.hpp", "kprof.hpp", "gemm_f32.hpp", "gemm_walk.hpp", "gemm_bf16.hpp", "gemm_split.hpp", "gemm_ring.hpp", "gemm_table.hpp", "gemm_launch.hpp", "plan.hpp", "plan_masks.hpp", "attention.hpp", "attention_export.hpp", "heads.hpp", "episode_stream.hpp", "graph_pool.hpp", "replay_prio.hpp", "td.hpp", "train_log.hpp", "record_common.hpp", "round_record.hpp", "decision_record.hpp", "attention_record.hpp", os.path.join("..", "..", "include", "melissa_hip.h")]
 
 
 def _hipcc() -> str:

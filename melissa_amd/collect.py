@@ -147,7 +147,7 @@ class RoundLoop:
                  eps: float = 0.0, episodes=None, rows_cap: int | None = None, use_graph: bool = False,
                  stream: "torch.cuda.Stream | None" = None, replay=None, episode_stream: "bool | str | None" = None,
                  ring: int = 16, discard: int = 0, graph_rounds: int = 4, eps_schedule: "EpsSchedule | None" = None,
-                 train_log=None, recorder=None, decisions=None):
+                 train_log=None, recorder=None, decisions=None, attention=None):
         """Episodes: by default a device STREAM (``melissa_amd.env.stream.EpisodeStream``: every reset draws a new episode
         like World.reset does, core.py:372-394; ``ring`` slots per env, ``discard`` construction-time samplings dropped);
         ``episodes`` = (packed, table) or ``episode_stream=False`` give a fixed table of ``episodes_per_env`` episodes;
@@ -166,8 +166,14 @@ class RoundLoop:
         ``decisions`` (:class:`melissa_amd.decision_record.DecisionRecorder` on ``venv``): every round, eager or captured, issues
         ``mel_decision_record_round`` BETWEEN the forward and ``mel_env_round`` - the only place where the round's logits, actions
         and ``live`` sets exist together - which books the policy's decisions by round index and by node degree.  It does not
-        touch the episode log: with or without ``recorder`` / ``train_log``.  None (the default): no such launch."""
+        touch the episode log: with or without ``recorder`` / ``train_log``.  None (the default): no such launch.
+        ``attention`` (:class:`melissa_amd.attention_record.AttentionRecorder` on ``venv`` and the policy's network, L-DGN or
+        DGN-R): every round, eager or captured, issues ``mel_forward_attention`` and ``mel_attention_record_round`` right behind
+        the decision recorder's place - conv2's coefficients of the round's agent rows, read back from the forward's workspace,
+        booked by round index, node degree and head.  It writes nothing the loop reads.  None (the default): no such launch."""
         self.venv, self.policy, self.eps, self.seed = venv, policy, eps, seed
+        check_rides("RoundLoop", "attention", attention, venv)
+        self.attention = attention
         check_rides("RoundLoop", "decisions", decisions, venv)
         self.decisions = decisions
         check_rides("RoundLoop", "recorder", recorder, venv)
@@ -207,6 +213,15 @@ class RoundLoop:
         self.logits = torch.zeros(self.rows_cap, self.n_actions, dtype=torch.float32, device=dev)
         self.act = torch.zeros(venv.env_num * venv.n if self.per_env_logits else self.rows_cap, dtype=torch.int32,
                                device=dev)
+        if attention is not None:
+            if self.per_env_logits:
+                raise ValueError("RoundLoop: attention records conv2's coefficients per agent row; an HL-DGN policy has no second "
+                                 "convolution and one logits row per env")
+            if attention.net is not policy.model:
+                raise ValueError("RoundLoop: attention was built for another network than the policy's")
+            if attention.rows_cap != self.rows_cap:
+                raise ValueError(f"RoundLoop: attention was built for another rows_cap ({attention.rows_cap}), the loop's forward "
+                                 f"runs with {self.rows_cap}")
         self.iterations = 0
         self._rounds_base = 0
         self.rounds = torch.zeros(1, dtype=torch.int32, device=dev)     # device-side round counter (RNG step, refill pacing)
@@ -266,6 +281,7 @@ class RoundLoop:
                                select=self._select, workspace=self.workspace, plan_ready=True,
                                integer_features=self.integer_features)
         self._launch_decisions(self.offsets)
+        self._launch_attention()
         self._bind_plan()
         self.venv.round_device(self.pool, self.act, self.offsets, self.live, self.table, round_counter=self.rounds,
                                replay=self.replay)
@@ -276,6 +292,11 @@ class RoundLoop:
         """What the forward just decided, with the state it decided in, into the decision tables and traces."""
         if self.decisions is not None:
             self.decisions.launch(self.logits, self.act, offsets, self.live)
+
+    def _launch_attention(self):
+        """Whom the forward's deciding agents attended to, with the state they decided in, into the attention tables."""
+        if self.attention is not None:
+            self.attention.launch(self.policy.model, self.workspace, self.rows_cap, self.offsets, self.live)
 
     def _launch_recorder(self):
         """The state the round just left, into the per-round curves and traces."""
@@ -624,8 +645,8 @@ class Collector:
     def __init__(self, policy, venv: HipGraphVectorEnv, episodes_per_env: int = 16, seed: int = 0, eps: float = 0.0,
                  replay=None, log_capacity: int = 65536, chunk: int = 8, use_graph: bool = True,
                  episode_stream: "bool | str | None" = None, ring: int = 16, stats: str = "episodes", recorder=None,
-                 decisions=None):
-        """``episode_stream`` / ``ring`` / ``recorder`` / ``decisions``: the episode supply, the per-round recorder and the decision recorder, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
+                 decisions=None, attention=None):
+        """``episode_stream`` / ``ring`` / ``recorder`` / ``decisions`` / ``attention``: the episode supply, the per-round recorder, the decision recorder and the attention recorder, as :class:`RoundLoop` takes them.  ``stats``: what ``info`` of a
         collect result summarises - ``"episodes"``: the final ``logger_stats`` row of each finished episode; ``"steps"``: the
         ``logger_stats`` of every env step played during the call, as the reference pools them
         (multi_agent_collector.py:276,316-322), accumulated by the env kernels (``HipGraphVectorEnv.enable_step_stats``)."""
@@ -637,7 +658,7 @@ class Collector:
             venv.enable_step_stats()            # before the loop: its `first` launch and every capture see the pool
         self.loop = RoundLoop(venv, policy, episodes_per_env=episodes_per_env, seed=seed, eps=eps, replay=replay,
                               use_graph=use_graph, episode_stream=episode_stream, ring=ring, recorder=recorder,
-                              decisions=decisions)
+                              decisions=decisions, attention=attention)
         self._decisions = self.loop.counters()["decisions"]
         self.collect_step, self.collect_episode, self.collect_time = 0, 0, 0.0
 
@@ -692,7 +713,8 @@ test_shares.__test__ = False           # (a helper, whatever the name says to py
 
 
 def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float = 0.0, seed: int = 0, use_graph: bool = True,
-                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None, recorder=None, decisions=None):
+                    chunk: int = 8, ring: int = 16, log_capacity: int | None = None, recorder=None, decisions=None,
+                    attention=None):
     """One pass over the evaluation schedule with all envs of ``venv`` at once: ``venv`` is built with ``is_testing=True,
     num_test_episodes=n_episode, spread_test_episodes=True``, so env b owns the list positions ``b, b + B, ...``
     (:func:`test_shares`; envs beyond the list own none).  The episodes come from the device sampler
@@ -711,7 +733,9 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     A ring of fewer than ``2 * chunk`` trace records could be overrun between two drains: ValueError.
     ``decisions`` (:class:`melissa_amd.decision_record.DecisionRecorder` on ``venv``): the same - reset, the shares as its quota,
     launched between every round's forward and env launch, drained after every chunk (``decisions.tables()`` /
-    ``decisions.drain_traces()``)."""
+    ``decisions.drain_traces()``).
+    ``attention`` (:class:`melissa_amd.attention_record.AttentionRecorder` on ``venv`` and the policy's network): the same once
+    more (``attention.tables()`` / ``attention.drain_traces()``)."""
     import time
     kw, B, T = venv._sampler_kw, venv.env_num, int(n_episode)
     if not kw["is_testing"] or int(kw["num_test_episodes"]) != T:
@@ -721,20 +745,21 @@ def evaluate_spread(policy, venv: HipGraphVectorEnv, n_episode: int, eps: float 
     shares = np.asarray(test_shares(T, B))
     capacity = int(log_capacity) if log_capacity is not None else max(1024, 16 * (T + B))
     t0 = time.perf_counter()
-    for name, rec in (("recorder", recorder), ("decisions", decisions)):
+    for name, rec in (("recorder", recorder), ("decisions", decisions), ("attention", attention)):
         check_rides("evaluate_spread", name, rec, venv, chunk=chunk)
     venv.scalars().zero_()                     # the episode cursors count from 0 again: this pass starts at the top
-    for rec in (recorder, decisions):
+    for rec in (recorder, decisions, attention):
         if rec is not None:
             rec.reset()
             rec.set_quota(shares)
     col = Collector(policy, venv, seed=seed, eps=eps, chunk=chunk, use_graph=use_graph, log_capacity=capacity,
-                    episode_stream="test", ring=ring, recorder=recorder, decisions=decisions)
+                    episode_stream="test", ring=ring, recorder=recorder, decisions=decisions,
+                    attention=attention)
     with torch.no_grad():
         while True:
             col.loop.run(col.chunk)
             sc = venv.scalars().cpu().numpy()                                     # synchronises
-            for rec in (recorder, decisions):
+            for rec in (recorder, decisions, attention):
                 if rec is not None:
                     rec.drain_traces()
             errors = int(np.bitwise_or.reduce(sc[:, _lib.S_ERROR]))

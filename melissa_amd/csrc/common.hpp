@@ -163,6 +163,14 @@ __device__ __forceinline__ int greedy_action(const float (&q)[8], float mean, fl
     return best;
 }
 
+// Values of one wavefront change hands through its LDS (lane a writes, lane b reads): the LDS operations of one wave complete
+// in order, the fences keep the compiler from moving the loads over the stores.  No other wave is waited for.
+__device__ __forceinline__ void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // ---- cross-lane reads with a WAVE-UNIFORM source lane: v_readlane (VALU -> SGPR), no LDS round trip ----
 __device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {

@@ -8,6 +8,7 @@
 #include "gemm_launch.hpp"
 #include "plan.hpp"
 #include "attention.hpp"
+#include "attention_export.hpp"   // mel_forward_attention: conv2's coefficients of the last agents forward (kernel: attention_record.hip)
 #include "heads.hpp"
 
 namespace mel {
@@ -878,6 +879,7 @@ size_t mel_abi_sizeof(int32_t which) {
         case 14: return sizeof(mel_train_log);
         case 15: return sizeof(mel_round_record);
         case 16: return sizeof(mel_decision_record);
+        case 17: return sizeof(mel_attention_record);
         default: return 0;
     }
 }
@@ -1228,6 +1230,37 @@ mel_status mel_forward_tap(const mel_weights* w, int32_t kind, int64_t bs, int32
         return fail(MEL_ERR_INVALID_ARG, "unknown tap kind %d", kind);
     if (e != hipSuccess) return fail(MEL_ERR_LAUNCH, "tap copy: %s", hipGetErrorString(e));
     return MEL_OK;
+}
+
+// the export kernel's view of a conv2 target descriptor is TargetDesc, member for member
+static_assert(sizeof(AgentRowDesc<1>) == sizeof(TargetDesc<1>) && sizeof(AgentRowDesc<2>) == sizeof(TargetDesc<2>), "AgentRowDesc");
+static_assert(offsetof(AgentRowDesc<2>, smask) == offsetof(TargetDesc<2>, smask) && offsetof(AgentRowDesc<2>, soff) == offsetof(TargetDesc<2>, soff) &&
+              offsetof(AgentRowDesc<1>, smask) == offsetof(TargetDesc<1>, smask) && offsetof(AgentRowDesc<1>, soff) == offsetof(TargetDesc<1>, soff),
+              "AgentRowDesc");
+
+mel_status mel_forward_attention(const mel_weights* w, int64_t bs, int32_t n, int64_t rows_cap, const void* workspace,
+                                 float* alpha, uint64_t* sources, void* stream) {
+    if (!w || !workspace || !alpha || !sources)
+        return fail(MEL_ERR_INVALID_ARG, "mel_forward_attention: null argument (w, workspace, alpha, sources)");
+    if (bs <= 0 || bs > (1 << 24) || n < 1 || n > MEL_MAX_NODES || rows_cap < 1 || rows_cap > bs * (int64_t)n)
+        return fail(MEL_ERR_INVALID_ARG, "mel_forward_attention: bs=%ld, n_nodes=%d or rows_cap=%ld outside [1, bs*n]", (long)bs, n, (long)rows_cap);
+    if (w->model != MEL_MODEL_LDGN && w->model != MEL_MODEL_DGNR)
+        return fail(MEL_ERR_UNSUPPORTED, "mel_forward_attention: model %d has no second convolution and no agent rows", w->model);
+    if (w->precision == MEL_PREC_BF16)
+        return fail(MEL_ERR_UNSUPPORTED, "mel_forward_attention: bf16 feature rows are not built");
+    if (w->precision < MEL_PREC_F32 || w->precision > MEL_PREC_F32_AUTO) return fail(MEL_ERR_INVALID_ARG, "precision=%d", w->precision);
+    clear_stale_error();
+    // Nothing the forward launches behind its conv2 attention writes x_l2 / x_r2, the conv2 descriptors or the row count (the
+    // heads read xcat and write hq / hpart), in row-list and in table mode alike: conv2's buffers hold rows in both.
+    const FwdLayout L = carve(w, make_dims(bs, n, rows_cap, false), const_cast<void*>(workspace));
+    const NetShape z = shape_of(w);
+    AttExportArgs a{};
+    a.xl = L.xl2, a.ld_l = z.srcw, a.xr = L.xr2, a.ld_r = z.hc, a.att = w->conv2.kind == MEL_CONV_GATV2 ? w->conv2.att : nullptr;
+    a.desc = L.plan.desc2, a.rows_dev = L.plan.offL + bs, a.rows_cap = (int)rows_cap;
+    a.heads = w->conv2.heads, a.kind = w->conv2.kind, a.score_scale = 1.0f / sqrtf((float)w->conv2.channels);
+    a.alpha = alpha, a.sources = sources;
+    return launch_attention_export(a, head_lanes(w->conv2.heads, w->conv2.channels), n, static_cast<hipStream_t>(stream),
+                                   "mel_forward_attention");
 }
 
 void* mel_prof_create(int32_t capacity) {

@@ -432,6 +432,22 @@ class HipForwardMixin:
         self._call(device, plan_ready, integer_features, "mel_ldgn_forward_agents", call)
         return out, row_offsets
 
+    def round_attention(self, workspace: torch.Tensor, bs: int, rows_cap: int, alpha: torch.Tensor, sources: torch.Tensor):
+        """conv2's attention coefficients of the last ``hip_forward_agents`` with this ``workspace`` and the same ``bs`` /
+        ``rows_cap`` (``mel_forward_attention``): ``alpha`` CUDA fp32 [rows_cap, 34, heads] - slot k = the row's k-th source in
+        ascending node id, 0 past the source count - and ``sources`` CUDA int64 [rows_cap, W] bit patterns, written for the
+        rows below the forward's row count only.  One launch, no host read: capturable.  -> (alpha, sources)."""
+        w = self._weights()
+        heads = int(w.conv2.heads) if self._MODEL != _lib.MODEL_HLDGN else 0
+        assert alpha.is_cuda and alpha.dtype == torch.float32 and alpha.is_contiguous() and \
+            alpha.numel() >= rows_cap * _lib.ATT_MAX_SOURCES * max(heads, 1)
+        assert sources.is_cuda and sources.dtype == torch.int64 and sources.is_contiguous() and \
+            sources.numel() >= rows_cap * _lib.set_words(self.agents_num)
+        _lib.check(_lib.load().mel_forward_attention(C.byref(w), bs, self.agents_num, rows_cap, workspace.data_ptr(),
+                                                     alpha.data_ptr(), sources.data_ptr(),
+                                                     _lib.current_stream_ptr(workspace.device)), "mel_forward_attention")
+        return alpha, sources
+
     def _prepare_obs(self, obs):
         if isinstance(obs, np.ndarray):                       # l_dgn.py:103-104
             obs = torch.as_tensor(obs, device=self.device)

@@ -42,6 +42,7 @@ import torch
 from .collect import Collector, RoundLoop, evaluate_spread
 from .env import HipGraphVectorEnv, connected_graph_pool, load_graph_pool
 from .policy import DQNPolicy
+from .attention_record import check_attention_args
 from .decision_record import check_decision_args
 from .round_record import check_record_args
 from .train import AGGREGATORS, N_DGN_NETWORK, build_network, check_network_args, load_policy_weights
@@ -82,7 +83,7 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
           dynamic_graph=True, feature_dtype="f32", heuristic=None, scripted_agents_ratio=0.0, spread=False, collect_stats="episodes",
           graphs=16, hidden_emb=128, num_heads=4, dueling_q_hidden_sizes=(128, 128), dueling_v_hidden_sizes=(128, 128),
           aggregator_function="max", attention_out=None, attention_rounds=8, curves_out=None, trace_out=None, trace_envs=1,
-          render_out=None, decisions_out=None, decision_trace_out=None):
+          render_out=None, decisions_out=None, decision_trace_out=None, attention_curves_out=None, attention_trace_out=None):
     """``graph_pool``: a list of graphs or the path of a packed ``.npz`` (``save_graph_pool``); None draws ``graphs`` connected
     random geometric graphs with the device generator (the graphs of ``synthetic_graph_pool(n_nodes, graphs)``).
     ``collect_stats``: "steps" reports the mean of every ``logger_stats`` key over every env step played (the reference's
@@ -99,9 +100,15 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
     the recorder rides behind the spread evaluation's rounds and leaves the returned dict as it is.
     ``decisions_out`` (a JSON file: :func:`melissa_amd.decision_record.summarise_decisions` of the evaluation's decisions plus the
     raw ``by_round`` / ``by_degree`` sums and the counters) and ``decision_trace_out`` (an ``.npz``: per round of envs
-    ``0 .. trace_envs - 1`` the deciding and relaying sets and the Q values, keyed like ``trace_out``) need ``spread`` too."""
+    ``0 .. trace_envs - 1`` the deciding and relaying sets and the Q values, keyed like ``trace_out``) need ``spread`` too.
+    ``attention_curves_out`` (a JSON file: :func:`melissa_amd.attention_record.summarise_attention` of conv2's coefficients of
+    the evaluation's own inference launches - the attention the informed and the waiting neighbours of every deciding node got,
+    by round index, node degree and head - plus the raw sums and the counters) and ``attention_trace_out`` (an ``.npz``: per
+    round of envs ``0 .. trace_envs - 1`` the deciding set and every deciding node's head-mean fields) need ``spread`` as well,
+    and a two-convolution model on an fp32 feature path."""
     check_record_args(spread, curves_out, trace_out, render_out, trace_envs)
     check_decision_args(spread, decisions_out, decision_trace_out, trace_envs)
+    check_attention_args(spread, attention_curves_out, attention_trace_out, trace_envs, model=model, feature_dtype=feature_dtype)
     check_network_args(model, hidden_emb, num_heads, dueling_q_hidden_sizes, dueling_v_hidden_sizes, aggregator_function,
                        feature_dtype=feature_dtype)
     if spread and collect_stats != "episodes":
@@ -134,8 +141,14 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         from .decision_record import DecisionRecorder
         traced = range(min(int(trace_envs), envs)) if decision_trace_out is not None else ()
         decisions = DecisionRecorder(venv, trace_envs=traced, trace_capacity=64)
+    attention = None
+    if attention_curves_out is not None or attention_trace_out is not None:
+        from .attention_record import AttentionRecorder
+        traced = range(min(int(trace_envs), envs)) if attention_trace_out is not None else ()
+        attention = AttentionRecorder(venv, net, trace_envs=traced, trace_capacity=64)
     if spread:
-        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed, recorder=recorder, decisions=decisions)
+        out, _positions = evaluate_spread(policy, venv, episodes, eps=0.0, seed=seed, recorder=recorder, decisions=decisions,
+                                          attention=attention)
     else:
         per_env = -(-episodes // envs) + 2
         col = Collector(policy, venv, episodes_per_env=per_env, seed=seed, eps=0.0, chunk=4, use_graph=envs >= 64,
@@ -145,6 +158,8 @@ def watch(model="l_dgn", n_nodes=20, envs=1, episodes=10, load=None, graph_pool=
         write_record(recorder, n_nodes, curves_out, trace_out, render_out)
     if decisions is not None:
         write_decisions(decisions, decisions_out, decision_trace_out)
+    if attention is not None:
+        write_attention(attention, attention_curves_out, attention_trace_out)
     if attention_out is not None:
         # AFTER the evaluation and on an env batch of its own (built like the evaluation's: same pool, seed and flags), so the
         # result below is what it is without the flag
@@ -204,6 +219,21 @@ def write_decisions(decisions, decisions_out=None, decision_trace_out=None) -> N
         save_decision_traces(decision_trace_out, traces)
 
 
+def write_attention(attention, attention_curves_out=None, attention_trace_out=None) -> None:
+    """What the attention recorder holds after an evaluation, into the files the caller asked for."""
+    from .attention_record import save_attention_traces, summarise_attention
+    by_round, by_degree, by_head, counters = attention.tables()
+    traces, lost = attention.drain_traces()
+    if attention_curves_out is not None:
+        doc = as_json(summarise_attention(by_round, by_degree, by_head))
+        doc.update(by_round_sums=by_round.tolist(), by_degree_sums=by_degree.tolist(), by_head_sums=by_head.tolist(),
+                   counters=dict(counters, lost_trace_records=int(lost)))
+        with open(attention_curves_out, "w") as f:
+            json.dump(doc, f)
+    if attention_trace_out is not None:
+        save_attention_traces(attention_trace_out, traces)
+
+
 def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     # (the three N-DGN scripts train these networks under their own names: a checkpoint of theirs loads into the same classes)
@@ -254,6 +284,13 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--decision-trace-out", default=argparse.SUPPRESS, metavar="FILE",
                     help=".npz that receives, per round of the traced envs (--trace-envs), who decided, who relayed and the Q "
                          "values; needs --spread")
+    ap.add_argument("--attention-curves-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help="JSON file that receives whom the deciding agents attended to in the evaluation's own inference launches "
+                         "(conv2: attention on informed / waiting neighbours, lifts, effective neighbours) per round index, node "
+                         "degree and head; needs --spread and a two-convolution model at an fp32 --dtype")
+    ap.add_argument("--attention-trace-out", default=argparse.SUPPRESS, metavar="FILE",
+                    help=".npz that receives, per round of the traced envs (--trace-envs), the deciding set and every deciding "
+                         "node's head-mean attention fields; needs --spread")
     return ap
 
 
@@ -266,6 +303,11 @@ def record_args(a: argparse.Namespace) -> tuple:
 def decision_args(a: argparse.Namespace) -> tuple:
     """(decisions_out, decision_trace_out) of a parsed command line, None where not given."""
     return getattr(a, "decisions_out", None), getattr(a, "decision_trace_out", None)
+
+
+def attention_args(a: argparse.Namespace) -> tuple:
+    """(attention_curves_out, attention_trace_out) of a parsed command line, None where not given."""
+    return getattr(a, "attention_curves_out", None), getattr(a, "attention_trace_out", None)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -283,6 +325,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     try:
         check_record_args(a.spread, *record_args(a))
         check_decision_args(a.spread, *decision_args(a), trace_envs=record_args(a)[3])
+        check_attention_args(a.spread, *attention_args(a), trace_envs=record_args(a)[3], model=a.model, feature_dtype=a.dtype)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -301,7 +344,8 @@ def main(argv=None):
                            dueling_v_hidden_sizes=list(a.dueling_v_hidden_sizes), aggregator_function=a.aggregator_function,
                            attention_out=a.attention_out, attention_rounds=a.attention_rounds,
                            **dict(zip(("curves_out", "trace_out", "render_out", "trace_envs"), record_args(a))),
-                           **dict(zip(("decisions_out", "decision_trace_out"), decision_args(a))))))
+                           **dict(zip(("decisions_out", "decision_trace_out"), decision_args(a))),
+                           **dict(zip(("attention_curves_out", "attention_trace_out"), attention_args(a))))))
 
 
 if __name__ == "__main__":

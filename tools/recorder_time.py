@@ -1,5 +1,6 @@
-"""Cost of a device recorder - the per-round recorder (melissa_amd/round_record.py: one more launch behind every env round) or the
-decision recorder (melissa_amd/decision_record.py: one more launch between every round's forward and env launch).
+"""Cost of a device recorder - the per-round recorder (melissa_amd/round_record.py: one more launch behind every env round), the
+decision recorder (melissa_amd/decision_record.py: one more launch between every round's forward and env launch) or the
+attention recorder (melissa_amd/attention_record.py: two more launches in the same place).
 
 The per-round time of the graph-replayed L-DGN round loop, three ways - recorder off, on without traces, on with four traced
 envs - on this tree and, with ``--parent-tree DIR`` (a checkout of the parent commit with its library built), on the parent's:
@@ -9,7 +10,7 @@ ALTERNATE: block k of every variant runs before block k + 1 of any, each tree in
 the median of the blocks with their minimum and maximum in microseconds per round, the spread (largest max - min of a variant),
 the recorder's cost on each tree and, per variant, this tree's median minus the parent's.
 
-    python tools/recorder_time.py --recorder round|decisions [--envs 1024] [--nodes 50] [--rounds 400] [--blocks 3]
+    python tools/recorder_time.py --recorder round|decisions|attention [--envs 1024] [--nodes 50] [--rounds 400] [--blocks 3]
                                   [--parent-tree DIR] [--out FILE]
 """
 import argparse
@@ -24,7 +25,8 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANTS = ("off", "on", "trace4")
 # --recorder -> (module, class, the RoundLoop argument)
-RECORDERS = {"round": ("round_record", "RoundRecorder", "recorder"), "decisions": ("decision_record", "DecisionRecorder", "decisions")}
+RECORDERS = {"round": ("round_record", "RoundRecorder", "recorder"), "decisions": ("decision_record", "DecisionRecorder", "decisions"),
+             "attention": ("attention_record", "AttentionRecorder", "attention")}
 
 
 def child(a):
@@ -49,7 +51,8 @@ def child(a):
                                  device="cuda", max_moves=48, construct_like_reference=False)
         kw = {}
         if variant != "off":
-            kw[arg] = Recorder(venv, trace_envs=range(4) if variant == "trace4" else (), trace_capacity=64)
+            own = (venv, net) if a.recorder == "attention" else (venv,)      # (the attention recorder reads the network's head count)
+            kw[arg] = Recorder(*own, trace_envs=range(4) if variant == "trace4" else (), trace_capacity=64)
         loop = RoundLoop(venv, DQNPolicy(net), seed=1, eps=0.05, use_graph=True, graph_rounds=a.graph_rounds, **kw)
         with torch.no_grad():
             loop.run(2 + 8 * a.graph_rounds)       # warm-up, both captures, past the first episodes
@@ -63,7 +66,7 @@ def child(a):
         if a.recorder == "round" and kw:
             out[variant + "_counters"] = kw[arg].curves()[2]
         elif kw:
-            by_round, by_degree, counters = kw[arg].tables()
+            _by_round, by_degree, *_by_head, counters = kw[arg].tables()
             out[variant + "_counters"] = dict(counters, booked=float(by_degree[:, 0].sum()))
         del loop, venv, net, kw
         gc.collect()
